@@ -18,7 +18,11 @@ torch.distributed.run, one rank per GPU):
 Algorithmic work per image comes from BASELINE.md §2 (per-resolution UNet / VAE GFLOP, attention
 quadratic in the token count), not a (res/512)^2 scaling.
 
-Also reported (rank 0):
+A plain run sets up, warms up, times `--steps` steps, writes the last timed step's outputs when `--dump-outputs DIR`
+is given (DIR/images_u8.npy [B, H, W, 3] and DIR/latents.npy [B, h, w, 4], float32; the inputs, weights and noise are
+seeded, so two builds run with the same arguments can be compared output for output) and prints the result line.
+
+With `--full` also reported (rank 0; `--no-roofline` / `--no-cpu-baseline` drop a leg of it):
   roofline     — the dominant MFMA kernel's algorithmic TFLOP/s (HIP events around every launch of it
                  during a profiled repeat of the timed steps) against the dense MFMA peak;
   cpu_baseline — BASELINE.md §3: the reference CPU path (fp32 PyTorch-CPU restatement, oracle/ — the
@@ -358,6 +362,27 @@ def throughput(batch: int, world: int, steps: int, elapsed: float) -> tuple:
     return batch * world * steps / elapsed, elapsed / steps * 1e3
 
 
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs: upper bound on what a run writes (all ranks together)
+
+
+def dump_outputs(out, directory: Path, rank: int, world: int) -> dict:
+    """The arrays a caller of the timed path receives (BatchResult.images_u8, .latents) of the last timed step as
+    float32 `<name>.npy` (`<name>_rank<r>.npy` when N > 1).  A batch whose float32 arrays exceed the rank's share of
+    DUMP_BYTES is cut to its leading images (a fixed sample: image i of the batch is always the same seeded input)."""
+    arrays = {"images_u8": out.images_u8, "latents": out.latents}
+    n = out.images_u8.shape[0]
+    per_image = sum(4 * t[0].numel() for t in arrays.values())
+    keep = max(1, min(n, DUMP_BYTES // world // per_image))
+    directory.mkdir(parents=True, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    written = {}
+    for name, t in arrays.items():
+        a = t[:keep].detach().to("cpu").numpy().astype(np.float32)
+        np.save(directory / f"{name}{suffix}.npy", a)
+        written[f"{name}{suffix}.npy"] = list(a.shape)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -368,11 +393,17 @@ def main():
     ap.add_argument("--sched-steps", type=int, default=50)
     ap.add_argument("--dtype", default=None, help="bf16 | fp16 | fp32 (default: the config's)")
     ap.add_argument("--vae-dtype", default=None, help="VAE compute type (default: the task's, fp16)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline profile, the CPU baseline and the parity report")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-images", type=int, default=4, help="configs[0] images for the CPU baseline (configs[0]: 4)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--opt", action="append", default=[], help="irx_set_option name=value (A/B experiments)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     spec = TASKS[args.task]
     batch = args.batch or spec["batch"]
     dtype = args.dtype or spec["dtype"]
@@ -414,8 +445,10 @@ def main():
     cfg_f = 2 if spec["guidance"] > 1 else 1
     tflop_img = (n_evals * cfg_f * F_UNET[res] + spec["n_enc"] * F_ENC[res] + F_DEC[res]) / 1000.0
 
+    dumped = dump_outputs(out, args.dump_outputs, rank, world) if args.dump_outputs is not None else None
+
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         torch.cuda.synchronize()
         graphs, eng.use_graphs = eng.use_graphs, False     # per-launch events need the eager launches
         L.profile_begin()
@@ -448,7 +481,7 @@ def main():
                     "buckets": bucket_summary(prof, args.steps)}
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if args.task != "denoise":
             dn = PipelineConfig.default("denoise")
             sds = {k: W.random_state_dict(k, getattr(dn, k), 0) for k in ("unet", "vae", "clip")}
@@ -471,7 +504,8 @@ def main():
                        "compute": f"UNet + CLIP {dtype}, VAE {vae_dtype} (fp32 accumulation)",
                        "parallelism": f"dp{world}", "weights_bcast": bcast,
                        "tflop_per_image": round(tflop_img, 2),
-                       "achieved_tflops_end_to_end": round(value * tflop_img, 1), "outputs_finite": finite},
+                       "achieved_tflops_end_to_end": round(value * tflop_img, 1), "outputs_finite": finite,
+                       "dumped_outputs": dumped},
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity,
         }
         print(json.dumps(line), flush=True)
