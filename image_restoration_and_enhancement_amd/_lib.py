@@ -58,6 +58,10 @@ class StepParams(C.Structure):
     ]
 
 
+class UnetOpts(C.Structure):
+    _fields_ = [("cfg_share", C.c_int), ("time_proj", C.c_void_p)]
+
+
 vp, i32, f32, sz, i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_long
 u64 = C.c_ulonglong
 # name: (restype, argtypes); every status-returning function is checked
@@ -86,6 +90,12 @@ _SIGS = {
     "irx_unet_prepare_context": (i32, [vp, vp, vp, i32, i32, vp, vp, sz]),
     "irx_unet_forward": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, sz]),
     "irx_unet_input_channels": (i32, [vp, C.POINTER(i32)]),
+    "irx_unet_workspace_bytes_ex": (i32, [vp, i32, i32, i32, vp, C.POINTER(sz)]),
+    "irx_unet_forward_ex": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, sz]),
+    "irx_unet_time_table_bytes": (i32, [vp, i32, C.POINTER(sz), C.POINTER(sz)]),
+    "irx_unet_time_table": (i32, [vp, vp, vp, i32, vp, vp, sz]),
+    "irx_op_gemm_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32]),
+    "irx_op_gemm_res_rows": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, i32]),
     "irx_vae_encode_workspace_bytes": (i32, [vp, i32, i32, i32, C.POINTER(sz)]),
     "irx_vae_encode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, sz]),
     "irx_vae_decode_workspace_bytes": (i32, [vp, i32, i32, i32, C.POINTER(sz)]),

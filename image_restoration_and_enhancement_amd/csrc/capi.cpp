@@ -54,6 +54,12 @@ static const X* as(const irx_model* h, int kind) {
 // images spanned by the rows of irx_op_gemm / irx_op_gemm_geglu (0: not image-indexed; tests of the canonical-batch
 // tile policy set it through irx_set_option("op_imgs", n))
 static int g_op_imgs = 0;
+// 1 (default): the pipelines run classifier-free-guidance batches through irx_unet_forward_ex with cfg_share
+// (0: irx_unet_forward, A/B and the bit-exactness tests); read by the host, not by the forward itself
+static int g_cfg_share = 1;
+// 1 (default): the pipelines compute every timestep's time-embedding projections once per loop (irx_unet_time_table)
+// and hand each evaluation its row (irx_unet_opts::time_proj); 0: the per-evaluation chain (A/B)
+static int g_temb_table = 1;
 
 extern "C" {
 
@@ -106,6 +112,8 @@ static const struct { const char* name; int* i; bool* b; } kOpts[] = {
     {"attn_prio", &g_attn_prio, nullptr},
     {"attn_qrep", &g_attn_qrep, nullptr},
     {"op_imgs", &g_op_imgs, nullptr},
+    {"cfg_share", &g_cfg_share, nullptr},
+    {"temb_table", &g_temb_table, nullptr},
     {"gemm_sk_blocks", &g_gemm_sk_blocks, nullptr},
     {"vae_attn_rows", &g_vae_attn_rows, nullptr},
     {"vae_flash", &g_vae_flash, nullptr},
@@ -308,6 +316,36 @@ int irx_unet_forward(irx_model* m, void* s, const void* x, int B, int h, int w, 
   IRX_API_BEGIN
   IRX_CHECK(x && t && kv && eps && ws, "null buffer");
   as<Unet>(m, IRX_MODEL_UNET)->forward(S(s), x, B, h, w, t, kv, L, eps, (char*)ws, cap);
+  IRX_API_END
+}
+int irx_unet_workspace_bytes_ex(const irx_model* m, int B, int h, int w, const irx_unet_opts* opts, size_t* bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(bytes && B > 0 && h > 0 && w > 0, "bad arguments");
+  *bytes = const_cast<Unet*>(as<Unet>(m, IRX_MODEL_UNET))
+               ->workspace_bytes(B, h, w, opts ? opts->cfg_share : 0, opts ? opts->time_proj : nullptr);
+  IRX_API_END
+}
+int irx_unet_forward_ex(irx_model* m, void* s, const void* x, int B, int h, int w, const float* t, const void* kv,
+                        int L, float* eps, const irx_unet_opts* opts, void* ws, size_t cap) {
+  IRX_API_BEGIN
+  const float* tp = opts ? opts->time_proj : nullptr;
+  IRX_CHECK(x && (t || tp) && kv && eps && ws, "null buffer");
+  IRX_CHECK(!tp || ((uintptr_t)tp % 16) == 0, "time_proj row must be 16-byte aligned");
+  as<Unet>(m, IRX_MODEL_UNET)->forward(S(s), x, B, h, w, t, kv, L, eps, (char*)ws, cap, opts ? opts->cfg_share : 0, tp);
+  IRX_API_END
+}
+int irx_unet_time_table_bytes(const irx_model* m, int n, size_t* table_bytes, size_t* ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(table_bytes && ws_bytes && n > 0, "bad arguments");
+  Unet* u = const_cast<Unet*>(as<Unet>(m, IRX_MODEL_UNET));
+  *table_bytes = (size_t)n * u->temb_cols() * sizeof(float);
+  *ws_bytes = u->time_table_ws(n);
+  IRX_API_END
+}
+int irx_unet_time_table(irx_model* m, void* s, const float* t, int n, float* table, void* ws, size_t cap) {
+  IRX_API_BEGIN
+  IRX_CHECK(t && table && ws, "null buffer");
+  as<Unet>(m, IRX_MODEL_UNET)->time_table(S(s), t, n, table, (char*)ws, cap);
   IRX_API_END
 }
 int irx_unet_input_channels(const irx_model* m, int* c) {
@@ -586,6 +624,32 @@ int irx_op_gemm(void* s, int dtype, int M, int N, int K, const void* A, long lda
   a.imgs = g_op_imgs;
   gemm(a, S(s));
   IRX_API_END
+}
+
+int irx_op_gemm_res_rows(void* s, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,
+                         const void* residual, long res_rows, void* C, int batch) {
+  IRX_API_BEGIN
+  GemmArgs a;
+  a.dtype = dtype; a.M = M; a.N = N; a.K = K;
+  a.A = A; a.lda = K; a.sA = (long)M * K;
+  a.B = B; a.ldb = K;
+  a.C = C; a.ldc = N; a.sC = (long)M * N;
+  a.bias = bias;
+  a.residual = residual; a.ldr = N; a.res_rows = res_rows;
+  a.batch = batch > 0 ? batch : 1;
+  a.imgs = g_op_imgs;
+  gemm(a, S(s));
+  IRX_API_END
+}
+
+size_t irx_op_gemm_workspace_bytes(int dtype, int M, int N, int K, int act, int out_f32, int imgs) {
+  GemmArgs a;
+  a.dtype = dtype; a.M = M; a.N = N; a.K = K;
+  a.A = (const void*)(uintptr_t)4096; a.lda = K;   // (aligned stand-ins, never read: a shape-only query)
+  a.B = (const void*)(uintptr_t)4096; a.ldb = K;
+  a.C = (void*)(uintptr_t)4096; a.ldc = N;
+  a.act = act; a.out_f32 = out_f32; a.imgs = imgs;
+  return gemm_workspace_bytes(a);
 }
 
 int irx_op_group_norm(void* s, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hw, int groups,

@@ -211,7 +211,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(GemmArgs a) {
         float v = acc[i][j][r] * a.alpha + bias;
         if (a.rowadd) v += a.rowadd[(long)(m / a.rows_per_group) * a.rowadd_ld + n];
         v = apply_act(v, a.act);
-        if (Rp) v += ld_f<T>(Rp + (long)m * a.ldr + n);
+        if (Rp) v += ld_f<T>(Rp + (a.res_rows && m >= a.res_rows ? m - a.res_rows : (long)m) * a.ldr + n);
         v *= a.out_scale;
         const long off = HS ? c_off(a, m, n) : (long)m * a.ldc + n;   // HS: head-split layout (small M only)
         if constexpr (OUTF32) ((float*)a.C)[(long)z * a.sC + off] = v;
@@ -284,6 +284,11 @@ static int small_splits(const GemmArgs& a) {
   return sp > 1 ? sp : 0;
 }
 
+size_t gemm_small_split_bytes(const GemmArgs& a) {
+  const int sp = small_splits(a);
+  return sp ? (size_t)sp * a.M * a.N * sizeof(float) : 0;
+}
+
 void gemm(const GemmArgs& a, hipStream_t s) {
   const int vec = a.dtype == F32 ? 4 : 8;
   IRX_CHECK(a.M > 0 && a.N > 0 && a.K > 0, "empty GEMM");
@@ -292,6 +297,11 @@ void gemm(const GemmArgs& a, hipStream_t s) {
   IRX_CHECK(a.hs_L == 0 || (a.batch == 1 && !a.geglu && a.hs_d % 8 == 0 && a.hs_C % a.hs_d == 0 &&
                             a.N % a.hs_C == 0 && a.M % a.hs_L == 0), "head-split output layout");
   IRX_CHECK(a.ldb % vec == 0 && ((uintptr_t)a.B % 16) == 0, "B rows must be 16-byte aligned");
+  // a repeating residual (GemmArgs::res_rows): the 16-bit epilogues of this file and gemm2.hip wrap the row; the
+  // batched (sR) and fp32 forms do not exist, and gemm_sk declines the call (gemm_sk_eligible)
+  IRX_CHECK(a.res_rows == 0 || (a.residual && is16(a.dtype) && a.batch == 1 && !a.geglu && a.res_rows > 0 &&
+                                a.res_rows < a.M && a.M <= 2 * a.res_rows),
+            "repeating residual (res_rows): 16-bit, batch 1, res_rows < M <= 2 res_rows");
   if (a.conv) {
     const ConvGeom& g = a.g;
     IRX_CHECK(g.src0 && g.C0 % vec == 0 && g.C1 % vec == 0, "conv channels must be 16-byte multiples");
@@ -339,7 +349,11 @@ void gemm(const GemmArgs& a, hipStream_t s) {
     p.batch = sp;
     p.sA = p.K;
     p.sB = p.K;
-    p.C = splitk_scratch((size_t)sp * a.M * a.N * sizeof(float));
+    // the caller's workspace when it gave one (the models: gemm_workspace_bytes reports these partials, so a captured
+    // graph never points into the library's scratch, which a later, larger call frees and reallocates); bare op
+    // calls fall back to that scratch
+    const size_t need = (size_t)sp * a.M * a.N * sizeof(float);
+    p.C = (a.splitk_ws && a.splitk_ws_bytes >= need) ? a.splitk_ws : (void*)splitk_scratch(need);
     p.hs_L = 0;           // partials row-major; the reduce kernel maps head-split rows (c_off)
     p.ldc = a.N;
     p.sC = (long)a.M * a.N;

@@ -1080,6 +1080,11 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm2_kern
       return m;
     }
   };
+  // residual row of GEMM row m: its pixel row, wrapped when the residual repeats (GemmArgs::res_rows)
+  auto rrow = [&](long m) -> long {
+    const long p = prow(m);
+    return a.res_rows && p >= a.res_rows ? p - a.res_rows : p;
+  };
   if constexpr (!OUTF32) {
     if (a.vec_epilogue) {
       // Staged through LDS: pass 1 (every wave) applies alpha/bias/row-add/act and writes the bf16 tile
@@ -1163,7 +1168,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm2_kern
       auto fetch = [&](int row, int c, Src& q) {
         const int m = m0 + row, n = n0 + c * 8;
         q.u = *(const uint4*)(tileS + row * BN + (csw(c, row) << 3));
-        if (Rp) q.r = *(const uint4*)(Rp + prow(m) * a.ldr + n);
+        if (Rp) q.r = *(const uint4*)(Rp + rrow(m) * a.ldr + n);
         if (a.rowadd) {
           const float4* ra = (const float4*)(a.rowadd + (long)(m / a.rows_per_group) * a.rowadd_ld + n);
           q.x = ra[0];
@@ -1244,7 +1249,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm2_kern
 #pragma unroll
                 for (int u = 0; u < kEpiPF; ++u) {
                   const int row = min(rg + (k0 + u) * RS, rend - 1);
-                  rres[u] = *(const uint4*)(Rp + prow(m0 + row) * a.ldr + n0 + cc * 8);
+                  rres[u] = *(const uint4*)(Rp + rrow(m0 + row) * a.ldr + n0 + cc * 8);
                 }
               }
 #pragma unroll
@@ -1366,7 +1371,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm2_kern
           }
           if (Rp) {
             float rv[8];
-            Vec16<T>::unpack(*(const uint4*)(Rp + prow(m) * a.ldr + n), rv);
+            Vec16<T>::unpack(*(const uint4*)(Rp + rrow(m) * a.ldr + n), rv);
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] += rv[e];
           }
@@ -1467,7 +1472,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs a, const fl
   }
   float rv[8];
   if (a.residual) {
-    const uint16_t* R = (const uint16_t*)a.residual + (long)z * a.sR + (long)m * a.ldr + n;
+    const long rm = a.res_rows && m >= a.res_rows ? m - a.res_rows : m;   // (GemmArgs::res_rows)
+    const uint16_t* R = (const uint16_t*)a.residual + (long)z * a.sR + rm * a.ldr + n;
     Vec16<T>::unpack(*(const uint4*)R, rv);
   }
 #pragma unroll
@@ -1516,7 +1522,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_gn_kernel(GemmArgs a, const
       f[0] += x.x; f[1] += x.y; f[2] += x.z; f[3] += x.w; f[4] += y.x; f[5] += y.y; f[6] += y.z; f[7] += y.w;
     }
     float rv[8];
-    if (a.residual) Vec16<T>::unpack(*(const uint4*)((const uint16_t*)a.residual + (long)m * a.ldr + n), rv);
+    const long rm = a.res_rows && m >= a.res_rows ? m - a.res_rows : m;   // (GemmArgs::res_rows)
+    if (a.residual) Vec16<T>::unpack(*(const uint4*)((const uint16_t*)a.residual + rm * a.ldr + n), rv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float v = f[e] * a.alpha + (a.bias ? a.bias[n + e] : 0.f);
@@ -1571,7 +1578,8 @@ void launch2_t(const GemmArgs& a, const Split& sp, hipStream_t s) {
   if (prof_on() && g_prof_shapes)
     nm += " [M " + std::to_string(a.M) + " N " + std::to_string(a.N) + " K " + std::to_string(a.K) +
           (a.conv ? " conv " + std::to_string(a.g.Hin) + "x" + std::to_string(a.g.Win) : std::string()) +
-          " split " + std::to_string(sp.splits) + (a.geglu ? " geglu" : "") + (a.residual ? " res" : "") +
+          " split " + std::to_string(sp.splits) + (a.geglu ? " geglu" : "") +
+          (a.residual ? (a.res_rows ? " reswrap" : " res") : "") +
           (a.ln_rs || a.ln_part ? " lnfold" : "") + (a.ln_out ? " lnout" : "") + (a.b_rows ? " bimg" : "") +
           (a.gn_part ? " gnpart" : "") + (a.up2_w ? " up2" : "") + "]";
   const GemmArgs& ea = a;
@@ -1971,15 +1979,17 @@ int dense_group_m(const GemmArgs& a, int bm, int bn, int resident, bool nmajor) 
 }
 
 size_t gemm_workspace_bytes(const GemmArgs& a) {
-  if (!g_large_tiles || !eligible(a)) return 0;
+  // the 4-wave kernel's small-M K splits (gemm.hip), should the large-tile path decline the call
+  const size_t small = gemm_small_split_bytes(a);
+  if (!g_large_tiles || !eligible(a)) return small;
   if (const int hbn = halo_bn(a)) {
     const int sp = halo_split_count(a, hbn);
     return sp > 1 ? (size_t)sp * ((a.M + 255) / 256 * 256) * a.N * sizeof(float) : 0;
   }
   const Choice c = choose(a);
-  if (c.BM == 0 || c.splits <= 1) return 0;
-  return (size_t)c.splits * a.batch * ((a.M + c.BM - 1) / c.BM * c.BM) * ((a.N + c.BN - 1) / c.BN * c.BN) *
-         sizeof(float);
+  if (c.BM == 0 || c.splits <= 1) return small;
+  return std::max(small, (size_t)c.splits * a.batch * ((a.M + c.BM - 1) / c.BM * c.BM) *
+                             ((a.N + c.BN - 1) / c.BN * c.BN) * sizeof(float));
 }
 
 // K splits of a halo conv (whole 64-channel slabs per split): 1 when the tiles fill the chip, 2 (in-kernel

@@ -163,9 +163,10 @@ void Model::gn_conv3(Ctx& c, const Act& x0, const Act* x1, P g, P gb, float eps,
 
 void Model::conv2d(Ctx& c, const Act& x0, const Act* x1, P w, P b, int cout, int k, int stride, int pad_t,
                    int pad_l, int hv, int wv, Act& out, const float* rowadd, long rowadd_ld,
-                   const void* residual, int out_f32, int ldc, bool stats) {
+                   const void* residual, int out_f32, int ldc, bool stats, long res_rows) {
   GemmArgs a = conv_args(dt_, x0, x1, ptr(w), b.set ? fptr(b) : nullptr, cout, k, stride, pad_t, pad_l, hv, wv, out,
                          rowadd, rowadd_ld, residual, out_f32, ldc);
+  a.res_rows = res_rows;
   run_gemm(c, a, stats && ldc < 0 ? &out : nullptr);
 }
 
@@ -190,7 +191,7 @@ void Model::run_gemm(Ctx& c, GemmArgs& a, Act* stats) {
 }
 
 void Model::linear(Ctx& c, const void* A, long lda, int M, int K, P w, int N, const float* bias, void* C, long ldc,
-                   int act, const void* residual, long ldr, int out_f32, int imgs, Act* stats) {
+                   int act, const void* residual, long ldr, int out_f32, int imgs, Act* stats, long res_rows) {
   GemmArgs a;
   a.dtype = dt_;
   a.M = M; a.N = N; a.K = K;
@@ -199,7 +200,7 @@ void Model::linear(Ctx& c, const void* A, long lda, int M, int K, P w, int N, co
   a.C = C; a.ldc = ldc;
   a.bias = bias;
   a.act = act;
-  a.residual = residual; a.ldr = ldr;
+  a.residual = residual; a.ldr = ldr; a.res_rows = res_rows;
   a.out_f32 = out_f32;
   a.imgs = imgs;
   run_gemm(c, a, stats && ldc == N ? stats : nullptr);
@@ -433,13 +434,13 @@ Unet::Unet(const irx_model_config& cfg, int dtype) : Model(IRX_MODEL_UNET, cfg, 
   kvw = mat(join(kv_names_), kv_cols_, cfg.cross_attention_dim);
 }
 
-Act Unet::resnet(Ctx& c, const ResW& r, Act& x0, Act* x1, const float* tproj, float eps) {
+Act Unet::resnet(Ctx& c, const ResW& r, Act& x0, Act* x1, const float* tproj, long tld, float eps) {
   const int B = x0.n, H = x0.h, W = x0.w;
   const int cin = x0.c + (x1 ? x1->c : 0);
   IRX_CHECK(cin == r.cin, "resnet channel mismatch");
   Act h1 = new_act(c, B, H, W, r.cout);
-  gn_conv3(c, x0, x1, r.n1w, r.n1b, eps, 1, r.c1w, r.c1b, r.cout, h1, tproj ? tproj + r.temb_off : nullptr,
-           temb_cols_, nullptr, true);
+  gn_conv3(c, x0, x1, r.n1w, r.n1b, eps, 1, r.c1w, r.c1b, r.cout, h1, tproj ? tproj + r.temb_off : nullptr, tld,
+           nullptr, true);
   Act sc;
   const void* res = x0.p;
   if (r.shortcut) {
@@ -480,7 +481,7 @@ void Unet::ln_gemm(Ctx& c, GemmArgs& g, const void* x, int rows, int C, P lnw, P
 }
 
 const float2* Unet::xf_proj(Ctx& c, const void* A, int M, int C, P w, const float* bias, void* out,
-                            const void* residual, int imgs, float2* lnp) {
+                            const void* residual, int imgs, float2* lnp, long res_rows) {
   GemmArgs a;
   a.dtype = dt_;
   a.M = M; a.N = C; a.K = C;
@@ -488,7 +489,7 @@ const float2* Unet::xf_proj(Ctx& c, const void* A, int M, int C, P w, const floa
   a.B = ptr(w); a.ldb = C;
   a.C = out; a.ldc = C;
   a.bias = bias;
-  a.residual = residual; a.ldr = C;
+  a.residual = residual; a.ldr = C; a.res_rows = res_rows;
   a.imgs = imgs;
   a.ln_out_rs = 1;
   a.ln_eps = 1e-5f;
@@ -498,9 +499,12 @@ const float2* Unet::xf_proj(Ctx& c, const void* A, int M, int C, P w, const floa
   return emit ? lnp : nullptr;
 }
 
-Act Unet::transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L) {
+Act Unet::transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L, bool dup) {
   const int B = x.n, HW = x.h * x.w, C = a.c;
   const long M = (long)B * HW;
+  // shared prefix (dup): B / M count the images / rows up to attn2.to_q, Bo / Mo those from cross-attention on
+  const int Bo = dup ? 2 * B : B;
+  const long Mo = dup ? 2 * M : M;
   const size_t es = dsize(dt_);
   const int heads = cfg_.heads, d = C / heads;
   const float scale = 1.0f / std::sqrt((float)d);
@@ -508,7 +512,7 @@ Act Unet::transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L) {
   // LayerNorm row statistics of the residual stream h, written by the projections that write it (GemmArgs::ln_out,
   // final (rstd, rstd * mean) rows: C == 320, the 64x64 level, where a 320-column tile holds the whole row; the
   // wider levels keep the statistics pass — their two-partial merge in the consumers' epilogues measured slower)
-  float2* lnp = (ln_fold_ && C == kLnGroup) ? (float2*)c.ws->alloc(M * sizeof(float2)) : nullptr;
+  float2* lnp = (ln_fold_ && C == kLnGroup) ? (float2*)c.ws->alloc(Mo * sizeof(float2)) : nullptr;
   const float2* parts = nullptr;
   // GroupNorm (no SiLU) -> proj_in: folded into per-image weights where they stay small next to the activation
   // (C == 320, the 64x64 level: 16 x 200 KB against 2 x 42 MB of gn_apply traffic; at 32x32 the 13 MB of per-image
@@ -549,9 +553,9 @@ Act Unet::transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L) {
     parts = xf_proj(c, gn.p, M, C, a.piw, fptr(a.pib), h.p, nullptr, B, lnp);
     drop(c, gn);
   }
-  void* n = c.ws->alloc(M * C * es);
+  void* n = c.ws->alloc(Mo * C * es);
   void* att = c.ws->alloc(M * C * es);
-  float2* st = ln_fold_ ? (float2*)c.ws->alloc(M * sizeof(float2)) : nullptr;   // LayerNorm row statistics
+  float2* st = ln_fold_ ? (float2*)c.ws->alloc(Mo * sizeof(float2)) : nullptr;   // LayerNorm row statistics
   // self-attention
   void* qkv = c.ws->alloc(M * 3 * C * es);
   // 16-bit engines: q|k|v written head-major ([q|k|v][image][head][token][d], GemmArgs::hs_*) so each attention
@@ -593,34 +597,44 @@ Act Unet::transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L) {
     if (hm) { g.hs_L = HW; g.hs_C = C; g.hs_d = d; }
     ln_gemm(c, g, h.p, M, C, a.ln2w, a.ln2b, a.q2u, a.q2v, nullptr, n, st, parts);
   }
-  if (!c.ws->dry()) {
+  // (dup: one launch per half of the guidance batch — the same B-image Q against that half's K|V; two launches of
+  // B images still fill the chip at the 64x64 level, and the attention kernels need no batch wrap for Q)
+  for (int half = 0; half < (dup ? 2 : 1) && !c.ws->dry(); ++half) {
     AttnArgs aa;
     aa.dtype = dt_; aa.B = B; aa.H = heads; aa.Lq = HW; aa.Lk = L; aa.d = d; aa.scale = scale;
     aa.q_scaled = dt_ != F32;
     if (hm) { aa.q = att; aa.ldq = d; aa.sq = (long)heads * HW * d; aa.hsq = (long)HW * d; }
     else { aa.q = att; aa.ldq = C; aa.sq = (long)HW * C; }
-    aa.k = (const char*)kv + a.kv_off * es; aa.ldk = kv_cols_; aa.sk = (long)L * kv_cols_;
-    aa.v = (const char*)kv + (a.kv_off + C) * es; aa.ldv = kv_cols_; aa.sv = aa.sk;
-    aa.o = n; aa.ldo = C; aa.so = (long)HW * C;
+    const long kv0 = (long)half * B * L * kv_cols_;
+    aa.k = (const char*)kv + (kv0 + a.kv_off) * es; aa.ldk = kv_cols_; aa.sk = (long)L * kv_cols_;
+    aa.v = (const char*)kv + (kv0 + a.kv_off + C) * es; aa.ldv = kv_cols_; aa.sv = aa.sk;
+    aa.o = (char*)n + half * M * C * es; aa.ldo = C; aa.so = (long)HW * C;
     attention(aa, c.s);
   }
-  parts = xf_proj(c, n, M, C, a.o2w, fptr(a.o2b), h.p, h.p, B, lnp);
+  if (dup) {   // the residual stream doubles here: both halves add the shared h (GemmArgs::res_rows)
+    Act h2 = new_act(c, Bo, x.h, x.w, C);
+    parts = xf_proj(c, n, Mo, C, a.o2w, fptr(a.o2b), h2.p, h.p, Bo, lnp, M);
+    drop(c, h);
+    h = h2;
+  } else {
+    parts = xf_proj(c, n, M, C, a.o2w, fptr(a.o2b), h.p, h.p, B, lnp);
+  }
   // GEGLU feed-forward: fused into the projection's epilogue when the large-tile path takes the shape
-  void* g = c.ws->alloc(M * 4 * C * es);
+  void* g = c.ws->alloc(Mo * 4 * C * es);
   {
     GemmArgs ga;
-    ga.dtype = dt_; ga.M = M; ga.N = 8 * C; ga.K = C;
+    ga.dtype = dt_; ga.M = Mo; ga.N = 8 * C; ga.K = C;
     ga.B = ptr(a.ffw); ga.ldb = C;
     ga.C = g; ga.ldc = 4 * C; ga.geglu = 1;
-    ga.imgs = B;
+    ga.imgs = Bo;
     ga.A = h.p; ga.lda = C;
     if (gemm_geglu_fusable(ga)) {
-      ln_gemm(c, ga, h.p, M, C, a.ln3w, a.ln3b, a.ffu, a.ffv, fptr(a.ffb), n, st, parts);
+      ln_gemm(c, ga, h.p, Mo, C, a.ln3w, a.ln3b, a.ffu, a.ffv, fptr(a.ffb), n, st, parts);
     } else {
-      void* ff = c.ws->alloc(M * 8 * C * es);
+      void* ff = c.ws->alloc(Mo * 8 * C * es);
       ga.geglu = 0; ga.C = ff; ga.ldc = 8 * C;
-      ln_gemm(c, ga, h.p, M, C, a.ln3w, a.ln3b, a.ffu, a.ffv, fptr(a.ffb), n, st, parts);
-      if (!c.ws->dry()) geglu(dt_, ff, 8 * C, M, 4 * C, g, 4 * C, 1, c.s);
+      ln_gemm(c, ga, h.p, Mo, C, a.ln3w, a.ln3b, a.ffu, a.ffv, fptr(a.ffb), n, st, parts);
+      if (!c.ws->dry()) geglu(dt_, ff, 8 * C, Mo, 4 * C, g, 4 * C, 1, c.s);
       c.ws->free(ff);
     }
   }
@@ -634,42 +648,45 @@ Act Unet::transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L) {
     c.ws->free(n);
     if (lnp) c.ws->free(lnp);
     Act ga;
-    ga.p = g; ga.n = B; ga.h = x.h; ga.w = x.w; ga.c = 4 * C;
-    Act out = new_act(c, B, x.h, x.w, C);
-    conv2d(c, h, &ga, a.pofw, a.pofb, C, 1, 1, 0, 0, x.h, x.w, out, nullptr, 0, x.p, 0, -1, true);
+    ga.p = g; ga.n = Bo; ga.h = x.h; ga.w = x.w; ga.c = 4 * C;
+    Act out = new_act(c, Bo, x.h, x.w, C);
+    conv2d(c, h, &ga, a.pofw, a.pofb, C, 1, 1, 0, 0, x.h, x.w, out, nullptr, 0, x.p, 0, -1, true, dup ? M : 0);
     c.ws->free(g);
     drop(c, h);
     return out;
   }
-  linear(c, g, 4 * C, M, 4 * C, a.ff2w, C, fptr(a.ff2b), h.p, C, ACT_NONE, h.p, C, 0, B);
+  linear(c, g, 4 * C, Mo, 4 * C, a.ff2w, C, fptr(a.ff2b), h.p, C, ACT_NONE, h.p, C, 0, Bo);
   c.ws->free(g);
   if (st) c.ws->free(st);
   c.ws->free(att);
   c.ws->free(n);
   if (lnp) c.ws->free(lnp);
-  Act out = new_act(c, B, x.h, x.w, C);
-  linear(c, h.p, C, M, C, a.pow, C, fptr(a.pob), out.p, C, ACT_NONE, x.p, C, 0, B, &out);
+  Act out = new_act(c, Bo, x.h, x.w, C);
+  linear(c, h.p, C, Mo, C, a.pow, C, fptr(a.pob), out.p, C, ACT_NONE, x.p, C, 0, Bo, &out, dup ? M : 0);
   drop(c, h);
   return out;
 }
 
-void Unet::run(Ctx& c, const void* x, int B, int h, int w, const float* t, const void* kv, int L, float* eps_out) {
+void Unet::run(Ctx& c, const void* x, int B, int h, int w, const float* t, const void* kv, int L, float* eps_out,
+               int cfg_share, const float* time_proj) {
+  IRX_CHECK(!cfg_share || B % 2 == 0, "cfg_share: the batch must be the two halves of a guidance batch (even)");
+  // Shared CFG prefix (16-bit engines): rows b and b + B / 2 are identical until the first cross-attention, so
+  // down_blocks.0.resnets.0 and its transformer up to attn2.to_q run on B / 2 images (transformer(dup)).  The
+  // engines are batch-invariant (kCanonImages), so those are the bits of rows [0, B / 2) of the full computation.
+  // conv_in stays at B images: its output is skips[0], which the last up resnet reads whole; the first resnet
+  // takes a view of its first half (the GroupNorm partial blocks are image-major, so the view covers them too).
+  const bool share = cfg_share && dt_ != F32 && down_[0].has_attn;
   const int* bo = cfg_.block_out_channels;
   const float eps = cfg_.norm_eps;
-  const size_t es = dsize(dt_);
-  // time embedding: sinusoid -> linear_1 -> SiLU -> linear_2, then SiLU(emb) (every resnet's input) and all
-  // resnets' time_emb_proj in one GEMM
-  void* te0 = c.ws->alloc((size_t)B * bo[0] * es);
-  void* te1 = c.ws->alloc((size_t)B * temb_dim_ * es);
-  void* te2 = c.ws->alloc((size_t)B * temb_dim_ * es);
-  float* tproj = (float*)c.ws->alloc((size_t)B * temb_cols_ * sizeof(float));
-  if (!c.ws->dry()) timestep_embed(dt_, t, B, bo[0], cfg_.flip_sin_to_cos, cfg_.freq_shift, te0, c.s);
-  linear(c, te0, bo[0], B, bo[0], t1w, temb_dim_, fptr(t1b), te1, temb_dim_, ACT_SILU, nullptr, 0, 0, B);
-  linear(c, te1, temb_dim_, B, temb_dim_, t2w, temb_dim_, fptr(t2b), te2, temb_dim_, ACT_SILU, nullptr, 0, 0, B);
-  linear(c, te2, temb_dim_, B, temb_dim_, tpw, temb_cols_, fptr(tpb), tproj, temb_cols_, ACT_NONE, nullptr, 0, 1, B);
-  c.ws->free(te0);
-  c.ws->free(te1);
-  c.ws->free(te2);
+  // time embedding: per image (time_chain), or — every image of the batch at one timestep — one row the caller
+  // computed ahead for the whole schedule (time_table), which every resnet's row add reads with a zero stride
+  float* tproj = const_cast<float*>(time_proj);
+  long tld = 0;
+  if (!time_proj) {
+    tproj = (float*)c.ws->alloc((size_t)B * temb_cols_ * sizeof(float));
+    tld = temb_cols_;
+    time_chain(c, t, B, tproj);
+  }
 
   Act xin;
   xin.p = const_cast<void*>(x); xin.n = B; xin.h = h; xin.w = w; xin.c = cin_pad_;
@@ -679,10 +696,13 @@ void Unet::run(Ctx& c, const void* x, int B, int h, int w, const float* t, const
   bool cur_is_skip = true;
   for (auto& blk : down_) {
     for (size_t j = 0; j < blk.res.size(); ++j) {
-      Act nx = resnet(c, blk.res[j], cur, nullptr, tproj, eps);
+      const bool dup = share && &blk == &down_[0] && j == 0;
+      Act src = cur;
+      if (dup) src.n = B / 2;
+      Act nx = resnet(c, blk.res[j], src, nullptr, tproj, tld, eps);
       if (!cur_is_skip) drop(c, cur);
       if (blk.has_attn) {
-        Act t2 = transformer(c, blk.attn[j], nx, kv, L);
+        Act t2 = transformer(c, blk.attn[j], nx, kv, L, dup);
         drop(c, nx);
         nx = t2;
       }
@@ -699,17 +719,17 @@ void Unet::run(Ctx& c, const void* x, int B, int h, int w, const float* t, const
     }
   }
   {
-    Act r = resnet(c, mid_res0_, cur, nullptr, tproj, eps);
+    Act r = resnet(c, mid_res0_, cur, nullptr, tproj, tld, eps);
     Act a = transformer(c, mid_attn_, r, kv, L);
     drop(c, r);
-    cur = resnet(c, mid_res1_, a, nullptr, tproj, eps);
+    cur = resnet(c, mid_res1_, a, nullptr, tproj, tld, eps);
     drop(c, a);
   }
   for (auto& blk : up_) {
     for (size_t j = 0; j < blk.res.size(); ++j) {
       Act skip = skips.back();
       skips.pop_back();
-      Act nx = resnet(c, blk.res[j], cur, &skip, tproj, eps);
+      Act nx = resnet(c, blk.res[j], cur, &skip, tproj, tld, eps);
       drop(c, cur);
       drop(c, skip);
       if (blk.has_attn) {
@@ -740,24 +760,60 @@ void Unet::run(Ctx& c, const void* x, int B, int h, int w, const float* t, const
     conv2d(c, gn, nullptr, conv_out_w, conv_out_b, cfg_.out_channels, 3, 1, 1, 1, h, w, o, nullptr, 0, nullptr, 1);
     drop(c, gn);
   }
-  c.ws->free(tproj);
+  if (!time_proj) c.ws->free(tproj);
 }
 
-size_t Unet::workspace_bytes(int B, int h, int w) {
+// sinusoid -> linear_1 -> SiLU -> linear_2, then SiLU(emb) (every resnet's input) and all resnets' time_emb_proj in
+// one GEMM: tproj fp32 [n][temb_cols_].  The small-M GEMMs choose their tiles and K splits from N and K only, so a
+// row's bits do not depend on n.
+void Unet::time_chain(Ctx& c, const float* t, int n, float* tproj) {
+  const int* bo = cfg_.block_out_channels;
+  const size_t es = dsize(dt_);
+  void* te0 = c.ws->alloc((size_t)n * bo[0] * es);
+  void* te1 = c.ws->alloc((size_t)n * temb_dim_ * es);
+  void* te2 = c.ws->alloc((size_t)n * temb_dim_ * es);
+  if (!c.ws->dry()) timestep_embed(dt_, t, n, bo[0], cfg_.flip_sin_to_cos, cfg_.freq_shift, te0, c.s);
+  linear(c, te0, bo[0], n, bo[0], t1w, temb_dim_, fptr(t1b), te1, temb_dim_, ACT_SILU, nullptr, 0, 0, n);
+  linear(c, te1, temb_dim_, n, temb_dim_, t2w, temb_dim_, fptr(t2b), te2, temb_dim_, ACT_SILU, nullptr, 0, 0, n);
+  linear(c, te2, temb_dim_, n, temb_dim_, tpw, temb_cols_, fptr(tpb), tproj, temb_cols_, ACT_NONE, nullptr, 0, 1, n);
+  c.ws->free(te0);
+  c.ws->free(te1);
+  c.ws->free(te2);
+}
+
+size_t Unet::time_table_ws(int n) {
   Arena ar;
   ar.reset(nullptr, 0);
   Ctx c{nullptr, &ar};
-  run(c, nullptr, B, h, w, nullptr, nullptr, 77, nullptr);
+  time_chain(c, nullptr, n, (float*)(uintptr_t)4096);
+  return ar.peak();
+}
+
+void Unet::time_table(hipStream_t s, const float* t, int n, float* table, char* ws, size_t cap) {
+  IRX_CHECK(blob_, "weights not bound");
+  // (rows equal to the per-evaluation chain's while the small-M path takes the GEMMs: gemm.hip small_splits)
+  IRX_CHECK(n > 0 && n <= 256, "time table: 1 .. 256 timesteps per call");
+  Arena ar;
+  ar.reset(ws, cap);
+  Ctx c{s, &ar};
+  time_chain(c, t, n, table);
+}
+
+size_t Unet::workspace_bytes(int B, int h, int w, int cfg_share, const float* time_proj) {
+  Arena ar;
+  ar.reset(nullptr, 0);
+  Ctx c{nullptr, &ar};
+  run(c, nullptr, B, h, w, nullptr, nullptr, 77, nullptr, cfg_share, time_proj);
   return ar.peak();
 }
 
 void Unet::forward(hipStream_t s, const void* x, int B, int h, int w, const float* t, const void* kv, int L,
-                   float* eps, char* ws, size_t cap) {
+                   float* eps, char* ws, size_t cap, int cfg_share, const float* time_proj) {
   IRX_CHECK(blob_, "weights not bound");
   Arena ar;
   ar.reset(ws, cap);
   Ctx c{s, &ar};
-  run(c, x, B, h, w, t, kv, L, eps);
+  run(c, x, B, h, w, t, kv, L, eps, cfg_share, time_proj);
 }
 
 void Unet::prepare_context(hipStream_t s, const void* ctx, int B, int L, void* kv, char* ws, size_t cap) {

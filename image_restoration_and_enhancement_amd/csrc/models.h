@@ -91,10 +91,11 @@ class Model {
   // `stats`: the output feeds a GroupNorm -> the epilogue also emits its partial sums when it can (Act::gnp)
   void conv2d(Ctx& c, const Act& x0, const Act* x1, P w, P b, int cout, int k, int stride, int pad_t, int pad_l,
               int hv, int wv, Act& out, const float* rowadd = nullptr, long rowadd_ld = 0,
-              const void* residual = nullptr, int out_f32 = 0, int ldc = -1, bool stats = false);
+              const void* residual = nullptr, int out_f32 = 0, int ldc = -1, bool stats = false,
+              long res_rows = 0);
   void linear(Ctx& c, const void* A, long lda, int M, int K, P w, int N, const float* bias, void* C, long ldc,
               int act = ACT_NONE, const void* residual = nullptr, long ldr = 0, int out_f32 = 0, int imgs = 0,
-              Act* stats = nullptr);
+              Act* stats = nullptr, long res_rows = 0);
   void run_gemm(Ctx& c, GemmArgs& a, Act* stats = nullptr);   // split-K partials / GroupNorm partials
   void gnorm(Ctx& c, const Act& x0, const Act* x1, P g, P b, float eps, int silu, const Act& out);
   // GroupNorm(+SiLU) of (x0 | x1) followed by a 3x3 / stride-1 / pad-1 conv into `out`: folded into the
@@ -130,11 +131,21 @@ class Unet : public Model {
  public:
   Unet(const irx_model_config& cfg, int dtype);
   int cin_pad() const { return cin_pad_; }
-  size_t workspace_bytes(int B, int h, int w);
+  // cfg_share: the caller promises that rows b and b + B / 2 carry the same input and timestep (the two halves of a
+  // classifier-free-guidance batch), so the 16-bit engines run everything up to the first cross-attention on B / 2
+  // images (run()); B must be even.  The fp32 engine ignores the promise (operation for operation the oracle).
+  // time_proj: one fp32 [temb_cols] row of time_table() that holds for every image of the batch (they share one
+  // timestep); run() then skips the time-embedding chain and does not read t.
+  size_t workspace_bytes(int B, int h, int w, int cfg_share = 0, const float* time_proj = nullptr);
+  // every resnet's time-embedding projection for n timesteps at once (t: device fp32 [n], n <= 256): table fp32
+  // [n][temb_cols()], row i bit-identical to what forward() computes for an image at t[i]
+  long temb_cols() const { return temb_cols_; }
+  size_t time_table_ws(int n);
+  void time_table(hipStream_t s, const float* t, int n, float* table, char* ws, size_t cap);
   size_t context_bytes(int B, int L) const { return (size_t)B * L * kv_cols_ * dsize(dt_); }
   void prepare_context(hipStream_t s, const void* ctx, int B, int L, void* kv, char* ws, size_t cap);
   void forward(hipStream_t s, const void* x, int B, int h, int w, const float* t, const void* kv, int L, float* eps,
-               char* ws, size_t cap);
+               char* ws, size_t cap, int cfg_share = 0, const float* time_proj = nullptr);
 
  private:
   struct XfW {
@@ -158,9 +169,14 @@ class Unet : public Model {
   };
   ResW make_res(const std::string& p, int cin, int cout);
   XfW make_xf(const std::string& p, int c);
-  void run(Ctx& c, const void* x, int B, int h, int w, const float* t, const void* kv, int L, float* eps);
-  Act resnet(Ctx& c, const ResW& r, Act& x0, Act* x1, const float* tproj, float eps);
-  Act transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L);
+  void run(Ctx& c, const void* x, int B, int h, int w, const float* t, const void* kv, int L, float* eps,
+           int cfg_share, const float* time_proj);
+  void time_chain(Ctx& c, const float* t, int n, float* tproj);
+  // (tld: row stride of tproj per image; 0: one row for the whole batch)
+  Act resnet(Ctx& c, const ResW& r, Act& x0, Act* x1, const float* tproj, long tld, float eps);
+  // dup: x holds the shared half of a classifier-free-guidance batch (run()): everything up to attn2.to_q runs on
+  // x.n images, cross-attention reads that Q against the K|V of 2 x.n images, and the result has 2 x.n images
+  Act transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L, bool dup = false);
   // LayerNorm(x) -> projection g (g.A / lda / bias set here): folded into g's epilogue when ln_fold_ and the shape
   // takes it — with the statistics from `parts` (the producer of x emitted them, GemmArgs::ln_out) or from a
   // statistics pass written to `st` — else through the normalised copy `nbuf`
@@ -168,8 +184,9 @@ class Unet : public Model {
                void* nbuf, float2* st, const float2* parts = nullptr);
   // a transformer projection that writes the residual stream (proj_in, to_out, to_out2): out = A W^T + bias
   // (+ residual), emitting the output's LayerNorm partials into `lnp` where the epilogue can; returns lnp or null
+  // (res_rows: the residual repeats every res_rows rows, GemmArgs::res_rows)
   const float2* xf_proj(Ctx& c, const void* A, int M, int C, P w, const float* bias, void* out, const void* residual,
-                        int imgs, float2* lnp);
+                        int imgs, float2* lnp, long res_rows = 0);
 
   int cin_pad_ = 8;
   bool ln_fold_ = false;   // LayerNorm folded into the transformer projections (fixed at creation: the blob layout)

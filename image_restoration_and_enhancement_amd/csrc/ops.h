@@ -35,6 +35,10 @@ struct GemmArgs {
   const float* bias = nullptr;                  // [N]
   const float* rowadd = nullptr; long rowadd_ld = 0; int rows_per_group = 1;  // += rowadd[(m/rpg)*ld + n]
   const void* residual = nullptr; long ldr = 0; long sR = 0;                  // += residual[m][n] (dtype)
+  // residual that repeats every res_rows rows (0: off): output row m >= res_rows adds residual row m - res_rows — the
+  // two halves of a classifier-free-guidance batch adding one shared half-batch tensor.  A per-row select, so tiles
+  // may straddle the wrap.  16-bit, batch 1, M <= 2 res_rows; the K = 320 streaming path does not take it.
+  long res_rows = 0;
   float out_scale = 1.f;
   int act = ACT_NONE;     // applied after bias/rowadd, before residual
   int batch = 1;
@@ -156,7 +160,10 @@ bool gemm_sk(const GemmArgs& a, hipStream_t s);           // K = 320 streaming p
 bool gemm_sk_eligible(const GemmArgs& a);
 extern int g_gemm_sk;      // 1: the K = 320 projections take gemm_sk (0: the large-tile kernel, A/B)
 extern int g_gemm_sk_blocks;
-size_t gemm_workspace_bytes(const GemmArgs& a);           // split-K partial buffer the call will use
+// split-K partial buffer the call will use (an upper bound: the large-tile splits or the 4-wave kernel's small-M
+// splits, whichever path ends up taking the call)
+size_t gemm_workspace_bytes(const GemmArgs& a);
+size_t gemm_small_split_bytes(const GemmArgs& a);         // ... the small-M part (gemm.hip; 0: no such splits)
 bool gemm_geglu_fusable(const GemmArgs& a);               // large-tile path can apply the GEGLU epilogue
 bool gemm_gn_fusable(const GemmArgs& a);                  // conv can apply GemmArgs::gn_ab to its operand
 bool gemm_ln_foldable(const GemmArgs& a);                 // large-tile epilogue can apply GemmArgs::ln_rs / ln_u

@@ -264,8 +264,41 @@ class UNet(NativeModel):
         L.call("irx_unet_input_channels", self.h, C.byref(c))
         self.cin_pad = c.value
 
-    def workspace_bytes(self, batch: int, h: int, w: int) -> int:
+    @staticmethod
+    def _opts(cfg_share: bool, time_proj: Optional[torch.Tensor]) -> L.UnetOpts:
+        return L.UnetOpts(int(cfg_share), None if time_proj is None else time_proj.data_ptr())
+
+    def workspace_bytes(self, batch: int, h: int, w: int, cfg_share: bool = False,
+                        time_proj: Optional[torch.Tensor] = None) -> int:
+        if cfg_share or time_proj is not None:
+            return self._size("irx_unet_workspace_bytes_ex", batch, h, w, C.byref(self._opts(cfg_share, time_proj)))
         return self._size("irx_unet_workspace_bytes", batch, h, w)
+
+    def temb_cols(self) -> int:
+        """Columns of a `time_table` row (the output channels of every resnet's time_emb_proj, concatenated)."""
+        tb, wb = C.c_size_t(), C.c_size_t()
+        L.call("irx_unet_time_table_bytes", self.h, 1, C.byref(tb), C.byref(wb))
+        return tb.value // 4
+
+    def time_table(self, t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """t: fp32 [n] on device -> every resnet's time-embedding projection per timestep, fp32 [n, temb_cols]:
+        row i is what `forward` computes for an image at t[i] (pass it as `time_proj`).  One chain for a whole
+        schedule; irx_unet_time_table takes up to 256 rows per call."""
+        n = t.numel()
+        assert t.dtype == torch.float32 and t.is_contiguous() and n > 0
+        tb, wb = C.c_size_t(), C.c_size_t()
+        L.call("irx_unet_time_table_bytes", self.h, n, C.byref(tb), C.byref(wb))
+        cols = tb.value // (4 * n)
+        if out is None:
+            out = torch.empty((n, cols), dtype=torch.float32, device=self.device)
+        assert out.shape == (n, cols) and out.is_contiguous()
+        for i in range(0, n, 256):
+            m = min(256, n - i)
+            L.call("irx_unet_time_table_bytes", self.h, m, C.byref(tb), C.byref(wb))
+            ws = self.workspace(wb.value)
+            L.call("irx_unet_time_table", self.h, self.stream(), C.c_void_p(t[i:].data_ptr()), m,
+                   C.c_void_p(out[i:].data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel())
+        return out
 
     def prepare_context(self, ctx: torch.Tensor) -> torch.Tensor:
         """Cross-attention K|V of every transformer block for ctx [B, L, 768] (dtype)."""
@@ -276,15 +309,25 @@ class UNet(NativeModel):
         return kv
 
     def forward(self, x: torch.Tensor, t: torch.Tensor, kv: torch.Tensor, ctx_len: int,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x: [B, h, w, cin_pad] (dtype); t: fp32 [B] on device -> eps fp32 [B, h, w, out_channels]."""
+                out: Optional[torch.Tensor] = None, cfg_share: bool = False,
+                time_proj: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x: [B, h, w, cin_pad] (dtype); t: fp32 [B] on device -> eps fp32 [B, h, w, out_channels].
+        `cfg_share`: rows b and b + B / 2 of x and t are identical (a classifier-free-guidance batch): the shared
+        prefix runs once.  `time_proj`: the `time_table` row of the timestep all B images are at, instead of the
+        per-evaluation time-embedding chain.  Both go through irx_unet_forward_ex and give the same bits out."""
         B, h, w, cp = x.shape
         assert cp == self.cin_pad and x.is_contiguous() and t.dtype == torch.float32 and t.numel() >= B
         if out is None:
             out = torch.empty((B, h, w, self.cfg.out_channels), dtype=torch.float32, device=self.device)
-        ws = self.workspace(self.workspace_bytes(B, h, w))
+        ws = self.workspace(self.workspace_bytes(B, h, w, cfg_share, time_proj))
         if _POISON:   # diagnostics (IRX_WS_POISON=1): every workspace byte 0xFF (a NaN in fp16 / bf16 / fp32) first
             ws.fill_(255)
+        if cfg_share or time_proj is not None:
+            assert time_proj is None or (time_proj.dtype == torch.float32 and time_proj.is_contiguous())
+            L.call("irx_unet_forward_ex", self.h, self.stream(), C.c_void_p(x.data_ptr()), B, h, w,
+                   C.c_void_p(t.data_ptr()), C.c_void_p(kv.data_ptr()), ctx_len, C.c_void_p(out.data_ptr()),
+                   C.byref(self._opts(cfg_share, time_proj)), C.c_void_p(ws.data_ptr()), ws.numel())
+            return out
         L.call("irx_unet_forward", self.h, self.stream(), C.c_void_p(x.data_ptr()), B, h, w,
                C.c_void_p(t.data_ptr()), C.c_void_p(kv.data_ptr()), ctx_len, C.c_void_p(out.data_ptr()),
                C.c_void_p(ws.data_ptr()), ws.numel())

@@ -166,6 +166,9 @@ class SDEngine:
             "slots": [torch.empty_like(lat) for _ in range(n_slots)],
             "cur": torch.empty_like(lat) if any(p.save_cur for p in plans) else None,
             "t_all": torch.tensor([[float(p.t)] * UB for p in plans], dtype=torch.float32).to(self.device),
+            # the schedule by plan position (PNDM repeats a timestep) and its time-embedding table (_loop_body)
+            "t_plan": torch.tensor([float(p.t) for p in plans], dtype=torch.float32).to(self.device),
+            "ttab": torch.empty((len(plans), self.unet.temb_cols()), dtype=torch.float32, device=self.device),
         }
 
     def denoise_loop(self, lat: torch.Tensor, kv: torch.Tensor, plans: List[StepPlan], guidance: float,
@@ -180,8 +183,9 @@ class SDEngine:
                                    self._loop_buffers(lat, plans, cfg_on))
         # the graph bakes in the UNet weight-blob pointer: the bound blob is part of the key (and each entry holds a
         # reference to it, so a rebind can neither replay stale weights nor let the old blob be freed under it)
+        # ... and so is the forward the loop takes (option cfg_share, _loop_body)
         key = (self.unet.blob.data_ptr(), tuple(lat.shape), tuple(kv.shape), bool(cfg_on), float(guidance),
-               mask_l is not None,
+               mask_l is not None, L.get_option("cfg_share"), L.get_option("temb_table"),
                tuple((p.t, p.mode, tuple(p.c), tuple(p.hw), p.e_div, p.e_mul, p.store_slot, tuple(p.hist),
                       p.x_from_cur, p.save_cur) for p in plans))
         cs = torch.cuda.current_stream(self.device)
@@ -238,10 +242,20 @@ class SDEngine:
         inpaint = int(mask_l is not None)
         cp = self.unet.cin_pad
         x_in, eps, slots, cur, t_all = bufs["x_in"], bufs["eps"], bufs["slots"], bufs["cur"], bufs["t_all"]
+        # both halves of a guidance batch are packed from the same latents with the same t: the UNet runs their
+        # shared prefix once (irx_unet_forward_ex; option cfg_share = 0: the plain forward, A/B)
+        share = bool(cfg_on) and L.get_option("cfg_share") != 0
+        # every image of an evaluation is at the plan's timestep, and the whole schedule is known here: the
+        # time-embedding chain runs once over all of it (inside a captured loop too) and each evaluation reads its
+        # row (16-bit engines; option temb_table = 0: the chain per evaluation, A/B)
+        ttab = None
+        if self.dt != L.IRX_F32 and L.get_option("temb_table") != 0:
+            ttab = self.unet.time_table(bufs["t_plan"], bufs["ttab"])
         L.call("irx_pack_unet_input", _stream(), self.dt, _p(lat), B, h, w, int(cfg_on), cp, inpaint, _p(mask_l),
                _p(masked_l), _p(x_in))
         for i, p in enumerate(plans):
-            self.unet.forward(x_in, t_all[i], kv, 77, out=eps)
+            self.unet.forward(x_in, t_all[i], kv, 77, out=eps, cfg_share=share,
+                              time_proj=None if ttab is None else ttab[i])
             sp = L.StepParams()
             sp.dtype, sp.batch, sp.h, sp.w = self.dt, B, h, w
             sp.eps, sp.cfg, sp.guidance = eps.data_ptr(), int(cfg_on), float(guidance)

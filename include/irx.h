@@ -141,6 +141,29 @@ int irx_unet_prepare_context(irx_model* m, void* stream, const void* ctx, int ba
 int irx_unet_forward(irx_model* m, void* stream, const void* x, int batch, int h, int w, const float* t,
                      const void* ctx_kv, int ctx_len, float* eps_out, void* ws, size_t ws_bytes);
 int irx_unet_input_channels(const irx_model* m, int* cin_pad);
+/* Extended forward.  opts->cfg_share != 0 is the caller's promise that rows b and b + batch / 2 of x and t are
+   identical — the [uncond x B, cond x B] batch of classifier-free guidance, whose halves differ only in ctx_kv.  The
+   16-bit engines then run everything up to the first cross-attention (down_blocks.0.resnets.0 and its transformer up
+   to attn2.to_q) on batch / 2 images; eps_out is bit-identical to irx_unet_forward on the same batch.  batch must be
+   even; the fp32 engine ignores the promise.
+   opts->time_proj != NULL: one row of irx_unet_time_table for the timestep every image of this batch is at; the
+   time-embedding chain is skipped and t is not read (may be NULL).  Give the workspace query the same opts.
+   opts == NULL or all zero: irx_unet_forward / irx_unet_workspace_bytes. */
+typedef struct irx_unet_opts {
+  int cfg_share;
+  const float* time_proj;   /* device fp32 [irx_unet_time_table row], 16-byte aligned */
+} irx_unet_opts;
+int irx_unet_workspace_bytes_ex(const irx_model* m, int batch, int h, int w, const irx_unet_opts* opts, size_t* bytes);
+int irx_unet_forward_ex(irx_model* m, void* stream, const void* x, int batch, int h, int w, const float* t,
+                        const void* ctx_kv, int ctx_len, float* eps_out, const irx_unet_opts* opts, void* ws,
+                        size_t ws_bytes);
+
+/* The time-embedding chain (sinusoid -> linear_1 -> SiLU -> linear_2 -> SiLU -> every resnet's time_emb_proj) for
+   the n timesteps of a whole schedule at once, n <= 256: t device fp32 [n] -> table fp32 [n][table_bytes / (4 n)],
+   row i bit-identical to what irx_unet_forward computes for an image at t[i].  The weights are streamed once per
+   loop instead of once per evaluation. */
+int irx_unet_time_table_bytes(const irx_model* m, int n, size_t* table_bytes, size_t* ws_bytes);
+int irx_unet_time_table(irx_model* m, void* stream, const float* t, int n, float* table, void* ws, size_t ws_bytes);
 
 /* ---- AutoencoderKL.encode / .decode (diffusers; img2img prepare_latents / final decode) ---- */
 int irx_vae_encode_workspace_bytes(const irx_model* m, int batch, int H, int W, size_t* bytes);
@@ -264,6 +287,14 @@ int irx_op_conv2d(void* stream, int dtype, const void* x0, const void* x1, int c
 int irx_op_gemm(void* stream, int dtype, int M, int N, int K, const void* A, long lda, const void* B, long ldb,
                 void* C, long ldc, const float* bias, float alpha, int act, const void* residual, long ldr,
                 int out_f32, int batch, long sA, long sB, long sC, long sR);
+/* C[M][N] = A[M][K] B[N][K]^T + bias + residual[m < res_rows ? m : m - res_rows][:] (all contiguous): the repeating
+   residual of the shared classifier-free-guidance prefix (irx_unet_forward_ex).  16-bit dtypes, batch 1 and
+   res_rows < M <= 2 res_rows only; anything else is an error. */
+int irx_op_gemm_res_rows(void* stream, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,
+                         const void* residual, long res_rows, void* C, int batch);
+/* split-K partial bytes a dense [M][K] x [N][K]^T GEMM of this shape takes from its caller's workspace (the models
+   carve them from their arena; bare irx_op_gemm calls use the library's scratch) */
+size_t irx_op_gemm_workspace_bytes(int dtype, int M, int N, int K, int act, int out_f32, int imgs);
 int irx_op_group_norm(void* stream, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hw,
                       int groups, float eps, const float* gamma, const float* beta, int silu, void* out, void* ws);
 size_t irx_op_group_norm_ws_bytes(int n, int hw, int groups);
