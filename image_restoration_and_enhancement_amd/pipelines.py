@@ -60,6 +60,34 @@ def draw_noise(seed: int, h: int, w: int, n: int) -> List[torch.Tensor]:
     return out
 
 
+def step_params(p: StepPlan, dt: int, lat: torch.Tensor, eps: torch.Tensor, cfg_on: bool, guidance: float,
+                slots: Sequence[torch.Tensor], cur: Optional[torch.Tensor], x_in: Optional[torch.Tensor], cin_pad: int,
+                mask_l: Optional[torch.Tensor] = None, masked_l: Optional[torch.Tensor] = None) -> L.StepParams:
+    """The `irx_sched_step` arguments of one plan of the denoising loop: the step updates `lat` [B, h, w, 4] in place
+    (from `cur` where the plan says so), reads and writes the history `slots` the plan names, and packs the next
+    UNet input into `x_in` (None on the last step)."""
+    B, h, w, _ = lat.shape
+    inpaint = int(mask_l is not None)
+    sp = L.StepParams()
+    sp.dtype, sp.batch, sp.h, sp.w = dt, B, h, w
+    sp.eps, sp.cfg, sp.guidance = eps.data_ptr(), int(cfg_on), float(guidance)
+    sp.hist_store = slots[p.store_slot].data_ptr() if p.store_slot is not None else None
+    for k in range(4):
+        sp.hist[k] = slots[p.hist[k]].data_ptr() if p.hist[k] is not None else None
+    for k in range(5):
+        sp.hw[k] = float(p.hw[k])
+    sp.e_div, sp.e_mul = float(p.e_div), float(p.e_mul)
+    sp.mode = p.mode
+    sp.c0, sp.c1, sp.c2, sp.c3 = (float(v) for v in p.c)
+    sp.x_src = (cur if p.x_from_cur else lat).data_ptr()
+    sp.cur_store = cur.data_ptr() if p.save_cur else None
+    sp.x_out = lat.data_ptr()
+    sp.unet_in = None if x_in is None else x_in.data_ptr()
+    sp.cin_pad, sp.inpaint = cin_pad, inpaint
+    sp.mask, sp.masked = (mask_l.data_ptr() if inpaint else None), (masked_l.data_ptr() if inpaint else None)
+    return sp
+
+
 class SDEngine:
     """The three native models of one task directory + the batched denoising loop."""
 
@@ -256,24 +284,9 @@ class SDEngine:
         for i, p in enumerate(plans):
             self.unet.forward(x_in, t_all[i], kv, 77, out=eps, cfg_share=share,
                               time_proj=None if ttab is None else ttab[i])
-            sp = L.StepParams()
-            sp.dtype, sp.batch, sp.h, sp.w = self.dt, B, h, w
-            sp.eps, sp.cfg, sp.guidance = eps.data_ptr(), int(cfg_on), float(guidance)
-            sp.hist_store = slots[p.store_slot].data_ptr() if p.store_slot is not None else None
-            for k in range(4):
-                sp.hist[k] = slots[p.hist[k]].data_ptr() if p.hist[k] is not None else None
-            for k in range(5):
-                sp.hw[k] = float(p.hw[k])
-            sp.e_div, sp.e_mul = float(p.e_div), float(p.e_mul)
-            sp.mode = p.mode
-            sp.c0, sp.c1, sp.c2, sp.c3 = (float(v) for v in p.c)
-            sp.x_src = (cur if p.x_from_cur else lat).data_ptr()
-            sp.cur_store = cur.data_ptr() if p.save_cur else None
-            sp.x_out = lat.data_ptr()
             last = i + 1 == len(plans)
-            sp.unet_in = None if last else x_in.data_ptr()
-            sp.cin_pad, sp.inpaint = cp, inpaint
-            sp.mask, sp.masked = (mask_l.data_ptr() if inpaint else None), (masked_l.data_ptr() if inpaint else None)
+            sp = step_params(p, self.dt, lat, eps, cfg_on, guidance, slots, cur, None if last else x_in, cp,
+                             mask_l, masked_l)
             L.call("irx_sched_step", _stream(), C.byref(sp))
         return lat
 

@@ -1,0 +1,416 @@
+"""The scheduler-step and pipeline glue kernels of csrc/elementwise.hip, each through its C entry point against the
+references in tests/glueref.py: irx_sched_step, irx_pack_unet_input, irx_latent_sample, irx_latents_to_vae,
+irx_image_to_tensor, irx_tensor_to_image.
+
+All but the posterior sample are compared BIT FOR BIT (as integer views, so -0.0 and NaN count): the kernels are
+built with -ffp-contract=off, their divisions are the correctly rounded sequence, and the references are the same
+fp32 operations in the same order.  Every output buffer is pre-filled with NaN bit patterns (an unwritten lane
+shows) and followed by a 64-element marker tail (a write past the end shows); a buffer a call must not write is
+compared whole with its content before the call.  Shapes are tiny: 15 pixels (less than a wave) and 273 pixels (two
+256-thread blocks, the last ragged; B = 3 so per-image and per-CFG-half offsets matter).
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from image_restoration_and_enhancement_amd import _lib as L
+from image_restoration_and_enhancement_amd.configs import SchedulerConfig
+from image_restoration_and_enhancement_amd.pipelines import _p, _stream, step_params
+from image_restoration_and_enhancement_amd.schedulers import make_planner
+from oracle import pipeline_ref as PR
+from tests import glueref as G
+
+pytestmark = pytest.mark.gpu
+
+DT = {"fp32": (L.IRX_F32, torch.float32), "bf16": (L.IRX_BF16, torch.bfloat16), "fp16": (L.IRX_F16, torch.float16)}
+SHAPES = [(1, 5, 3), (3, 7, 13)]
+TAIL = 64
+GUIDANCE = 5.0
+SF = 0.18215
+_INT = {4: torch.int32, 2: torch.int16, 1: torch.uint8}
+# (cin_pad, inpaint) per storage width: the fp32 pack writes channel by channel (9 = no pad lanes at all), the 16-bit
+# one 16-byte chunks: one chunk, two, and the zero-chunk loop of the engine's 64
+PADS = {4: [(8, 0), (9, 0), (9, 1), (16, 0), (16, 1)], 2: [(8, 0), (16, 0), (16, 1), (64, 0), (64, 1)]}
+
+
+def bits(t):
+    return t.contiguous().view(-1).view(_INT[t.element_size()])
+
+
+def same(got, want):
+    return got.dtype == want.dtype and got.shape == want.shape and torch.equal(bits(got).cpu(), bits(want).cpu())
+
+
+def first_diff(got, want):
+    d = (bits(got).cpu() != bits(want).cpu()).nonzero().view(-1)
+    i = int(d[0])
+    return f"{d.numel()} of {got.numel()} differ, first at flat index {i}: got {got.view(-1)[i].item()!r}, " \
+           f"want {want.view(-1)[i].item()!r}"
+
+
+class Buf:
+    """A device buffer a kernel may write: `shape` elements holding `data` (or, if None, NaN bit patterns / 0xA5
+    bytes), then TAIL marker elements; `lead` elements in front shift it off its allocation's alignment."""
+
+    def __init__(self, device, shape, dtype, data=None, lead=0):
+        n = int(np.prod(shape))
+        self.shape, self.n, self.lead = tuple(shape), n, lead
+        self.buf = torch.empty(lead + n + TAIL, dtype=dtype, device=device)
+        if dtype == torch.uint8:
+            self.buf.fill_(0xA5)
+            self.buf[lead + n:] = 0x3C
+        else:
+            self.buf.fill_(float("nan"))
+            self.buf[lead + n:] = 1234.0
+        self.t = self.buf[lead:lead + n].view(shape)
+        if data is not None:
+            if isinstance(data, np.ndarray):
+                data = torch.from_numpy(np.ascontiguousarray(data))
+            self.t.copy_(data.to(dtype))
+        self.before = self.buf.clone()
+
+    def expect(self, want, what):
+        """After a call: the payload is `want` (fp32 NumPy reference, rounded to the storage type here; None: what it
+        held before the call), and lead and tail are untouched."""
+        torch.cuda.synchronize()
+        full = self.before.cpu().clone()
+        if want is not None:
+            if isinstance(want, np.ndarray):
+                want = torch.from_numpy(np.ascontiguousarray(want))
+            assert tuple(want.shape) == self.shape, (what, want.shape, self.shape)
+            full[self.lead:self.lead + self.n] = want.to(self.buf.dtype).reshape(-1)
+        got = self.buf.cpu()
+        lo, hi = self.lead, self.lead + self.n
+        assert same(got[hi:], full[hi:]) and same(got[:lo], full[:lo]), f"{what}: wrote outside the buffer"
+        assert same(got[lo:hi], full[lo:hi]), f"{what}: {first_diff(got[lo:hi], full[lo:hi])}"
+        self.before = self.buf.clone()
+
+
+def _dev(a, device):
+    """A device copy; the caller keeps it in a local until the call that reads it is issued."""
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def _rand(rng, *shape):
+    return rng.standard_normal(shape).astype(np.float32)
+
+
+def _plan_forms():
+    """One plan of every form the planners emit, taken from the planners themselves."""
+    p = make_planner(SchedulerConfig(kind="pndm"))
+    p.set_timesteps(20)
+    ts, _ = p.get_timesteps(20, 1.0)
+    pl = p.plan(ts)
+    forms = {"pndm_save_cur": pl[0], "pndm_x_from_cur": pl[1], "pndm_hist2": pl[2], "pndm_hist3": pl[3],
+             "pndm_hist4": pl[4]}
+    nh = {k: sum(h is not None for h in v.hist) for k, v in forms.items()}
+    assert forms["pndm_save_cur"].save_cur and nh["pndm_save_cur"] == 0
+    assert forms["pndm_x_from_cur"].x_from_cur and forms["pndm_x_from_cur"].store_slot is None
+    assert (nh["pndm_x_from_cur"], forms["pndm_x_from_cur"].e_div) == (1, 2.0)
+    assert (nh["pndm_hist2"], forms["pndm_hist2"].e_div) == (1, 2.0) and forms["pndm_hist2"].hw[:2] == (3.0, -1.0)
+    assert (nh["pndm_hist3"], forms["pndm_hist3"].e_div) == (2, 12.0)
+    assert nh["pndm_hist4"] == 3 and forms["pndm_hist4"].e_mul == float(np.float32(1 / 24))
+    d = make_planner(SchedulerConfig(kind="ddim"))
+    d.set_timesteps(30)
+    ts, _ = d.get_timesteps(30, 0.6)
+    forms["ddim"] = d.plan(ts)[3]
+    assert forms["ddim"].mode == 1 and all(v.mode == 0 for k, v in forms.items() if k != "ddim")
+    return forms
+
+
+FORMS = _plan_forms()
+
+
+def _inpaint_inputs(rng, B, h, w):
+    mask = rng.integers(0, 2, (B, h, w)).astype(np.float32)
+    mask[0, 0, 0] = 0.3                   # the mask travels as a value, not as a flag
+    return mask, _rand(rng, B, h, w, 4)
+
+
+# ------------------------------------------------------------------------------------------------ irx_sched_step
+def _one_step(device, dtype, shape, plan, cfg, cin_pad, inpaint, seed, with_unet_in=True):
+    dt, tdt = DT[dtype]
+    B, h, w = shape
+    rng = np.random.default_rng(seed)
+    UB = 2 * B if cfg else B
+    eps_u = _rand(rng, B, h, w, 4)
+    eps_c = _rand(rng, B, h, w, 4) if cfg else None
+    x, cur_np = _rand(rng, B, h, w, 4), _rand(rng, B, h, w, 4)
+    slots_np = [_rand(rng, B, h, w, 4) for _ in range(5)]
+    mask, masked = _inpaint_inputs(rng, B, h, w) if inpaint else (None, None)
+    what = f"{dtype} {shape} cfg={cfg} cin_pad={cin_pad} inpaint={inpaint} unet_in={with_unet_in}"
+
+    eps_d = _dev(np.concatenate([eps_u, eps_c]) if cfg else eps_u, device)
+    lat = Buf(device, (B, h, w, 4), torch.float32, x)
+    # the slot / cur a plan stores into is not read by it: pre-filled with NaN
+    slots = [Buf(device, (B, h, w, 4), torch.float32, None if s == plan.store_slot else slots_np[s])
+             for s in range(5)]
+    cur = Buf(device, (B, h, w, 4), torch.float32, None if plan.save_cur else cur_np)
+    x_in = Buf(device, (UB, h, w, cin_pad), tdt)
+    mask_d, masked_d = _dev(mask, device), _dev(masked, device)
+    sp = step_params(plan, dt, lat.t, eps_d, bool(cfg), GUIDANCE, [s.t for s in slots], cur.t,
+                     x_in.t if with_unet_in else None, cin_pad, mask_d, masked_d)
+    L.call("irx_sched_step", _stream(), C.byref(sp))
+
+    cur_l = [cur_np]
+    ref = G.emulate_step(plan, eps_u, eps_c, GUIDANCE, x, slots_np, cur_l, cin_pad, mask, masked)
+    lat.expect(ref.x, what + " x_out")
+    for s in range(5):
+        slots[s].expect(ref.eps if s == plan.store_slot else None, what + f" slot {s}")
+    cur.expect(ref.cur if plan.save_cur else None, what + " cur")
+    x_in.expect(ref.unet_in if with_unet_in else None, what + " unet_in")
+    if with_unet_in and cfg:
+        assert same(x_in.t[:B], x_in.t[B:]), what + ": CFG halves differ"
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("dtype", list(DT))
+def test_sched_step_bit_exact(device, dtype, shape, form):
+    """One irx_sched_step == emulate_step, bit for bit, on x_out, hist_store, cur_store and unet_in; whatever the plan
+    does not store (NULL hist_store / cur_store, NULL unet_in) stays as it was.  Exact equality is the claim: no FMA
+    (-ffp-contract=off) and correctly rounded fp32 divisions."""
+    plan = FORMS[form]
+    seed = 0
+    for cfg in (0, 1):
+        for cin_pad, inpaint in PADS[DT[dtype][1].itemsize]:
+            seed += 1
+            _one_step(device, dtype, shape, plan, cfg, cin_pad, inpaint, seed)
+    _one_step(device, dtype, shape, plan, 1, 16, 1, 99, with_unet_in=False)
+
+
+# ------------------------------------------------------------------------------------------------ whole schedule
+SCHEDULES = {"pndm20_s0.5": ("pndm", 20, 0.5, False), "pndm20_s1.0": ("pndm", 20, 1.0, False),
+             "ddim30_s0.6": ("ddim", 30, 0.6, True)}
+
+
+@pytest.mark.parametrize("sched", list(SCHEDULES))
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("dtype", list(DT))
+def test_schedule_on_device(device, dtype, shape, sched):
+    """A whole planned schedule through irx_sched_step with the loop's buffers and arguments (in-place x_src == x_out,
+    rotating history slots, cur saved and reused): after every step the latents equal the chained emulate_step bit
+    for bit and the oracle scheduler at test_scheduler.py's tolerance, and the packed UNet input is the new latents
+    rounded to the storage type, in both CFG halves."""
+    kind, n, strength, inpaint = SCHEDULES[sched]
+    dt, tdt = DT[dtype]
+    B, h, w = shape
+    cin_pad = (9 if inpaint else 8) if dtype == "fp32" else 64
+    rng = np.random.default_rng(7)
+    p = make_planner(SchedulerConfig(kind=kind))
+    p.set_timesteps(n)
+    ts, _ = p.get_timesteps(n, strength)
+    plans = p.plan(ts)
+    ref = PR.PNDMRef() if kind == "pndm" else PR.DDIMRef()
+    ref.set_timesteps(n)
+
+    x = _rand(rng, B, h, w, 4)
+    xr = torch.from_numpy(x.copy())
+    mask, masked = _inpaint_inputs(rng, B, h, w) if inpaint else (None, None)
+    mask_d, masked_d = _dev(mask, device), _dev(masked, device)
+    # the buffers of SDEngine._loop_buffers
+    n_slots = max([(-1 if q.store_slot is None else q.store_slot) for q in plans] + [-1]) + 1
+    lat = Buf(device, (B, h, w, 4), torch.float32, x)
+    eps_d = torch.empty((2 * B, h, w, 4), dtype=torch.float32, device=device)
+    slots = [Buf(device, (B, h, w, 4), torch.float32) for _ in range(n_slots)]
+    cur = Buf(device, (B, h, w, 4), torch.float32) if any(q.save_cur for q in plans) else None
+    x_in = Buf(device, (2 * B, h, w, cin_pad), tdt)
+    slots_np, cur_np = [None] * 5, [None]
+
+    for i, (plan, t) in enumerate(zip(plans, ts)):
+        eu, ec = _rand(rng, B, h, w, 4), _rand(rng, B, h, w, 4)
+        eps_d.copy_(torch.from_numpy(np.concatenate([eu, ec])))
+        last = i + 1 == len(plans)
+        sp = step_params(plan, dt, lat.t, eps_d, True, GUIDANCE, [s.t for s in slots],
+                         None if cur is None else cur.t, None if last else x_in.t, cin_pad, mask_d, masked_d)
+        L.call("irx_sched_step", _stream(), C.byref(sp))
+        o = G.emulate_step(plan, eu, ec, GUIDANCE, x, slots_np, cur_np, cin_pad, mask, masked)
+        x = o.x
+        what = f"{sched} {dtype} {shape} step {i} (t={int(t)})"
+        lat.expect(x, what + " latents")
+        for s in range(n_slots):
+            slots[s].expect(o.eps if s == plan.store_slot else None, what + f" slot {s}")
+        if cur is not None:
+            cur.expect(o.cur if plan.save_cur else None, what + " cur")
+        x_in.expect(None if last else o.unet_in, what + " unet_in")
+        if not last:
+            new = torch.from_numpy(x).to(tdt)
+            assert same(x_in.t[:B, ..., :4].cpu(), new) and same(x_in.t[B:, ..., :4].cpu(), new), what
+        e = torch.from_numpy(eu) + GUIDANCE * (torch.from_numpy(ec) - torch.from_numpy(eu))
+        xr = ref.step(e, int(t), xr)
+        np.testing.assert_allclose(lat.t.cpu().numpy(), xr.numpy(), rtol=2e-5, atol=2e-5, err_msg=what)
+
+
+# ------------------------------------------------------------------------------------------------ irx_pack_unet_input
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("dtype", list(DT))
+def test_pack_unet_input_bit_exact(device, dtype, shape):
+    dt, tdt = DT[dtype]
+    B, h, w = shape
+    rng = np.random.default_rng(3)
+    for cfg in (0, 1):
+        for cin_pad, inpaint in PADS[tdt.itemsize]:
+            lat = _rand(rng, B, h, w, 4)
+            mask, masked = _inpaint_inputs(rng, B, h, w) if inpaint else (None, None)
+            out = Buf(device, ((2 if cfg else 1) * B, h, w, cin_pad), tdt)
+            lat_d, mask_d, masked_d = _dev(lat, device), _dev(mask, device), _dev(masked, device)
+            L.call("irx_pack_unet_input", _stream(), dt, _p(lat_d), B, h, w, cfg, cin_pad, inpaint, _p(mask_d),
+                   _p(masked_d), _p(out.t))
+            out.expect(G.pack_unet_input(lat, cfg, cin_pad, mask, masked),
+                       f"{dtype} {shape} cfg={cfg} cin_pad={cin_pad} inpaint={inpaint}")
+
+
+# ------------------------------------------------------------------------------------------------ rejected layouts
+REJECTED = {  # name: (dtype, cin_pad, inpaint, lead elements, pass the mask)
+    "bf16_cin_pad_12": ("bf16", 12, 0, 0, True), "fp16_cin_pad_12": ("fp16", 12, 0, 0, True),
+    "bf16_inpaint_cin_pad_8": ("bf16", 8, 1, 0, True), "fp16_inpaint_cin_pad_8": ("fp16", 8, 1, 0, True),
+    "bf16_misaligned": ("bf16", 8, 0, 1, True), "fp16_misaligned": ("fp16", 16, 1, 1, True),
+    "bf16_inpaint_null_mask": ("bf16", 16, 1, 0, False), "fp32_inpaint_null_mask": ("fp32", 9, 1, 0, False),
+}
+
+
+@pytest.mark.parametrize("entry", ["irx_pack_unet_input", "irx_sched_step"])
+@pytest.mark.parametrize("case", list(REJECTED))
+def test_rejected_layouts(device, case, entry):
+    """Layouts the 16-byte stores of the 16-bit pack cannot take, and inpaint without its inputs, are refused on the
+    host (IrxError): nothing launches and every buffer stays at its pre-fill."""
+    dtype, cin_pad, inpaint, lead, with_mask = REJECTED[case]
+    dt, tdt = DT[dtype]
+    B, h, w = 1, 5, 3
+    rng = np.random.default_rng(5)
+    x = _rand(rng, B, h, w, 4)
+    mask, masked = _inpaint_inputs(rng, B, h, w)
+    mask_d = _dev(mask, device) if with_mask else None
+    masked_d = _dev(masked, device)
+    out = Buf(device, (2 * B, h, w, cin_pad), tdt, lead=lead)
+    lat = Buf(device, (B, h, w, 4), torch.float32, x)
+    if lead:
+        assert out.t.data_ptr() % 16 != 0 and out.buf.data_ptr() % 16 == 0
+    with pytest.raises(L.IrxError):
+        if entry == "irx_pack_unet_input":
+            L.call(entry, _stream(), dt, _p(lat.t), B, h, w, 1, cin_pad, inpaint, _p(mask_d), _p(masked_d), _p(out.t))
+        else:
+            eps_d = _dev(_rand(rng, 2 * B, h, w, 4), device)
+            sp = step_params(FORMS["ddim"], dt, lat.t, eps_d, True, GUIDANCE, [], None, out.t, cin_pad,
+                             _dev(mask, device) if inpaint else None, masked_d if inpaint else None)
+            if not with_mask:
+                sp.mask = None
+            assert sp.inpaint == inpaint
+            L.call(entry, _stream(), C.byref(sp))
+    out.expect(None, case + " destination")
+    lat.expect(None, case + " latents")
+
+
+# ------------------------------------------------------------------------------------------------ irx_image_to_tensor
+def _all_bytes_image():
+    """1 x 16 x 48 x 3: pixel p holds (p + 85 c) % 256 in channel c, so every channel sees every byte value three
+    times (once under each of three mask values)."""
+    p = np.arange(16 * 48)
+    img = np.stack([(p + 85 * c) % 256 for c in range(3)], axis=-1).astype(np.uint8).reshape(1, 16, 48, 3)
+    mask = np.array([0.0, 0.49, 0.5, 1.0], dtype=np.float32)[(p // 256 + p) % 4].reshape(1, 16, 48)
+    for c in range(3):
+        for keep in (True, False):
+            assert len(set(img[..., c][(mask < 0.5) == keep].tolist())) == 256
+    return img, mask
+
+
+@pytest.mark.parametrize("with_mask", [False, True])
+@pytest.mark.parametrize("cpad", [8, 3])
+@pytest.mark.parametrize("dtype", list(DT))
+def test_image_to_tensor_exhaustive(device, dtype, cpad, with_mask):
+    dt, tdt = DT[dtype]
+    img, mask = _all_bytes_image()
+    if not with_mask:
+        mask = None
+    out = Buf(device, (1, 16, 48, cpad), tdt)
+    img_d, mask_d = _dev(img, device), _dev(mask, device)
+    L.call("irx_image_to_tensor", _stream(), dt, _p(img_d), _p(mask_d), 1, 16, 48, cpad, _p(out.t))
+    out.expect(G.image_to_tensor(img, cpad, mask), f"{dtype} cpad={cpad} mask={with_mask}")
+    assert not bits(out.t[..., 3:]).any()          # pad channels: +0.0 exactly
+
+
+# ------------------------------------------------------------------------------------------------ irx_tensor_to_image
+def _t2img(device, dtype, x_cpu, with_f01, what):
+    """x_cpu: [B, H, W, ldc] in the storage type.  The uint8 output is pre-filled with the complement of the expected
+    bytes, so an unwritten byte cannot pass."""
+    dt, tdt = DT[dtype]
+    B, H, W_, ldc = x_cpu.shape
+    u8, f01 = G.tensor_to_image(x_cpu.float().numpy())
+    img = Buf(device, (B, H, W_, 3), torch.uint8, 255 - u8)
+    f = Buf(device, (B, H, W_, 3), torch.float32)
+    x_d = x_cpu.to(device)
+    L.call("irx_tensor_to_image", _stream(), dt, _p(x_d), B, H, W_, ldc, _p(img.t), _p(f.t) if with_f01 else None)
+    img.expect(u8, what + " uint8")
+    f.expect(f01 if with_f01 else None, what + " f01")
+
+
+@pytest.mark.parametrize("with_f01", [True, False])
+@pytest.mark.parametrize("ldc", [4, 3])
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_tensor_to_image_all_16bit_values(device, dtype, ldc, with_f01):
+    """Every finite fp16 / bf16 bit pattern as an input pixel value (the non-finite ones replaced by 0); with
+    ldc = 4, as in decode, the unread fourth channel holds NaN."""
+    tdt = DT[dtype][1]
+    v = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16).view(tdt)
+    v = torch.where(torch.isfinite(v.float()), v, torch.zeros_like(v))
+    assert torch.isfinite(v.float()).all() and len(set(bits(v).tolist())) > 63400
+    B, H, W_ = 2, 3, 3641
+    x = torch.full((B * H * W_, ldc), float("nan"), dtype=tdt)
+    x[:, :3] = torch.cat([v, v[:2]]).view(-1, 3)
+    _t2img(device, dtype, x.view(B, H, W_, ldc), with_f01, f"{dtype} ldc={ldc}")
+
+
+@pytest.mark.parametrize("with_f01", [True, False])
+@pytest.mark.parametrize("ldc", [4, 3])
+def test_tensor_to_image_fp32_ties_and_clamp(device, ldc, with_f01):
+    """fp32 inputs around every k + 0.5 boundary of v * 255 (tests/test_glue_host.py shows the grid holds exact ties
+    at even and odd k), below -1 and above 1."""
+    g = torch.from_numpy(G.t2img_fp32_grid()).view(-1, 3)
+    x = torch.full((g.shape[0], ldc), float("nan"), dtype=torch.float32)
+    x[:, :3] = g
+    _t2img(device, "fp32", x.view(1, 1, -1, ldc), with_f01, f"fp32 ldc={ldc}")
+
+
+# ------------------------------------------------------------------------------------------------ irx_latents_to_vae
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("dtype", list(DT))
+def test_latents_to_vae_bit_exact(device, dtype, shape):
+    dt, tdt = DT[dtype]
+    B, h, w = shape
+    lat = _rand(np.random.default_rng(11), B, h, w, 4) * np.float32(3.0)
+    out = Buf(device, (B, h, w, 8), tdt)
+    lat_d = _dev(lat, device)
+    L.call("irx_latents_to_vae", _stream(), dt, _p(lat_d), B, h, w, SF, _p(out.t))
+    out.expect(G.latents_to_vae(lat, SF), f"{dtype} {shape}")
+    want = (torch.from_numpy(lat) / float(np.float32(SF))).to(tdt)
+    assert same(out.t[..., :4].cpu(), want) and not bits(out.t[..., 4:]).any()
+
+
+# ------------------------------------------------------------------------------------------------ irx_latent_sample
+@pytest.mark.parametrize("with_noise", [False, True])
+@pytest.mark.parametrize("bcast", [0, 1])
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("dtype", list(DT))
+def test_latent_sample_within_rounding_budget(device, dtype, shape, bcast, with_noise):
+    """Posterior sample (+ add_noise) against float64 on the same rounded moments.  expf is not bit-reproducible, so
+    each element is held to the rounding budget 8 * 2^-24 * (|a| |sf| (|mean| + std |eps|) + |b noise|): six fp32
+    roundings and a 1-ulp expf (tests/test_glue_host.py: an fp32 restatement on the CPU stays inside it)."""
+    dt, tdt = DT[dtype]
+    B, h, w = shape
+    a, b = make_planner(SchedulerConfig(kind="ddim")).add_noise_coeffs(501) if with_noise else (1.0, 0.0)
+    mom, eps, noise = G.latent_case(tdt, B, h, w, bcast, with_noise)
+    out = Buf(device, (B, h, w, 4), torch.float32)
+    mom_d, eps_d, noise_d = mom.to(device), _dev(eps, device), _dev(noise, device)
+    L.call("irx_latent_sample", _stream(), dt, _p(mom_d), B, h, w, _p(eps_d), _p(noise_d), bcast, SF, a, b, _p(out.t))
+    torch.cuda.synchronize()
+    assert same(out.buf[out.n:], out.before[out.n:]), "wrote past the end"
+    got = out.t.cpu().numpy().astype(np.float64)
+    ref, budget = G.latent_sample_f64(mom.float().numpy(), eps, noise, bcast, SF, a, b)
+    assert np.isfinite(got).all()
+    err = np.abs(got - ref)
+    worst = float((err / np.maximum(budget, 1e-300)).max()) * G.LATENT_BOUND_ULPS
+    print(f"latent_sample {dtype} {shape} bcast={bcast} noise={with_noise}: worst {worst:.2f} of "
+          f"{G.LATENT_BOUND_ULPS} units of 2^-24")
+    assert (err <= budget).all(), worst

@@ -1,6 +1,7 @@
 """CPU tests: scheduler constants and grids (known-answer values), and the host-side step planner
-(`schedulers.py`) driven through a float32 emulation of the fused `irx_sched_step` kernel against the
-oracle's diffusers-0.35.2 restatement (`oracle/pipeline_ref.py` PNDMRef / DDIMRef).
+(`schedulers.py`) driven through a float32 emulation of the fused `irx_sched_step` kernel (`tests/glueref.py`;
+`tests/test_glue_gpu.py` holds the kernel to it bit for bit) against the oracle's diffusers-0.35.2 restatement
+(`oracle/pipeline_ref.py` PNDMRef / DDIMRef).
 
 Known answers are derived by hand from the saved scheduler configs
 (`outputs/models/*/best/scheduler/scheduler_config.json`: scaled_linear betas 0.00085..0.012, 1000 train
@@ -13,6 +14,7 @@ import torch
 from image_restoration_and_enhancement_amd import schedulers as S
 from image_restoration_and_enhancement_amd.configs import SchedulerConfig
 from oracle import pipeline_ref as PR
+from tests.glueref import emulate_step
 
 
 def test_alphas_cumprod_known_values():
@@ -47,28 +49,6 @@ def test_pndm_full_grid_duplicate():
     assert p.timesteps[:4].tolist() == [951, 901, 901, 851] and len(p.timesteps) == 21
 
 
-def emulate_step(plan: S.StepPlan, eps_u, eps_c, guidance, x, slots, cur):
-    """float32 restatement of step_kernel (csrc/elementwise.hip) for one plan."""
-    f = np.float32
-    e0 = (eps_u + f(guidance) * (eps_c - eps_u)) if eps_c is not None else eps_u
-    if plan.store_slot is not None:
-        slots[plan.store_slot] = e0.copy()
-    e = f(plan.hw[0]) * e0
-    for k in range(4):
-        if plan.hist[k] is not None:
-            e = e + f(plan.hw[k + 1]) * slots[plan.hist[k]]
-    e = e / f(plan.e_div)
-    e = f(plan.e_mul) * e
-    xs = cur[0] if plan.x_from_cur else x
-    if plan.save_cur:
-        cur[0] = xs.copy()
-    c0, c1, c2, c3 = (f(v) for v in plan.c)
-    if plan.mode == 0:
-        return c0 * xs - (c1 * e) / c2
-    x0 = (xs - c0 * e) / c1
-    return c2 * x0 + c3 * e
-
-
 @pytest.mark.parametrize("kind,n,strength,guidance", [("pndm", 20, 0.5, 5.0), ("pndm", 20, 1.0, 7.5),
                                                       ("pndm", 30, 0.75, 7.5), ("pndm", 20, 0.8, 0.0),
                                                       ("ddim", 30, 0.6, 5.0), ("ddim", 50, 0.5, 5.0)])
@@ -87,7 +67,7 @@ def test_planner_matches_oracle_scheduler(kind, n, strength, guidance):
     for plan, t in zip(plans, ts):
         eu = rng.standard_normal(x.shape).astype(np.float32)
         ec = rng.standard_normal(x.shape).astype(np.float32) if guidance > 1 else None
-        x = emulate_step(plan, eu, ec, guidance, x, slots, cur)
+        x = emulate_step(plan, eu, ec, guidance, x, slots, cur).x
         e = torch.from_numpy(eu) + guidance * (torch.from_numpy(ec) - torch.from_numpy(eu)) if ec is not None \
             else torch.from_numpy(eu)
         xr = ref.step(e, int(t), xr)
