@@ -11,7 +11,7 @@
 // v_mfma_f32_16x16x4_f32.  Tiles are staged global -> VGPR -> LDS (double buffered, one barrier
 // per K step, next tile's loads in flight under the current tile's MFMAs) with a bank-spreading
 // XOR swizzle; block -> tile mapping is XCD-aware.
-#include "ops.h"
+#include "gemm_plan.h"
 #include "profile.h"
 
 namespace irx {
@@ -265,30 +265,6 @@ void launch_t(const GemmArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool g_large_tiles = true;   // irx_set_option("large_tiles", 0) forces the 4-wave kernel (A/B tests)
-int g_small_splitk = 1;
-
-// K splits for a small-M GEMM on the 4-wave kernel (the CLIP text model's 154 rows, the time embedding's 2B rows): a
-// few 64-column tiles over a long K leave most CUs idle (the CLIP fc2 [154 x 768 x 3072]: 36 blocks, 50 us).  The
-// splits depend on N and K only (every M <= 256 takes the same ones: batch-invariant), whole 64-deep K steps each,
-// and not on the output layout (a head-split q|k|v projection takes the same splits as its row-major twin).
-static int small_splits(const GemmArgs& a) {
-  if (!g_small_splitk || !is16(a.dtype) || a.conv || a.batch != 1 || a.geglu || a.A1 || a.up2_w) return 0;
-  if (a.M > 256 || a.N % 8 || a.K < 1024 || a.N <= 16) return 0;
-  if (a.out_f32 ? a.ldc % 4 != 0 : (a.ldc % 8 != 0 || ((uintptr_t)a.C % 16) != 0)) return 0;
-  if (a.residual && (a.ldr % 8 != 0 || ((uintptr_t)a.residual % 16) != 0)) return 0;
-  const long ctiles = (a.N + 63) / 64;
-  if (ctiles >= 128) return 0;
-  int sp = 1;
-  while (sp < 8 && ctiles * sp * 2 <= 256 && a.K % (sp * 2 * 64) == 0 && a.K / (sp * 2) >= 256) sp *= 2;
-  return sp > 1 ? sp : 0;
-}
-
-size_t gemm_small_split_bytes(const GemmArgs& a) {
-  const int sp = small_splits(a);
-  return sp ? (size_t)sp * a.M * a.N * sizeof(float) : 0;
-}
-
 void gemm(const GemmArgs& a, hipStream_t s) {
   const int vec = a.dtype == F32 ? 4 : 8;
   IRX_CHECK(a.M > 0 && a.N > 0 && a.K > 0, "empty GEMM");
@@ -315,63 +291,58 @@ void gemm(const GemmArgs& a, hipStream_t s) {
     IRX_CHECK(!a.A1 || (a.batch == 1 && a.kA1 > 0 && a.kA1 < a.K && a.lda1 % vec == 0 && ((uintptr_t)a.A1 % 16) == 0),
               "second A source: batch 1, 0 < kA1 < K, 16-byte rows");
   }
-  IRX_CHECK(!(a.ln_rs || a.ln_part) || (a.ln_u && gemm_ln_foldable(a)), "folded LayerNorm needs the large-tile path");
   IRX_CHECK(!a.ln_part || (a.ln_T >= 1 && a.K == a.ln_T * kLnGroup), "LayerNorm partials must cover the K row");
-  if (a.geglu) {
-    IRX_CHECK(gemm_geglu_fusable(a) && gemm_large_tile(a, s), "GEGLU epilogue needs the large-tile path");
-    return;
-  }
-  if (a.ln_rs || a.ln_part) {
-    IRX_CHECK(gemm_large_tile(a, s), "folded LayerNorm needs the large-tile path");
-    return;
-  }
-  if (a.ln_out || a.b_rows) {
-    IRX_CHECK((!a.ln_out || gemm_emits_ln_parts(a)) && (!a.b_rows || gemm_bimg_ok(a)) && gemm_large_tile(a, s),
-              "LayerNorm partials / per-image weights need the large-tile epilogue");
-    return;
-  }
-  if (a.gn_part) {
-    IRX_CHECK(gemm_emits_gn_parts(a) > 0 && gemm_large_tile(a, s), "GroupNorm partials need the large-tile epilogue");
-    return;
-  }
-  if (a.gn_ab) {
-    IRX_CHECK(gemm_gn_fusable(a) && gemm_large_tile(a, s), "GroupNorm-fused operand needs the halo conv path");
-    return;
-  }
-  if (a.dtype != F32 && g_large_tiles && gemm_large_tile(a, s)) return;
-  IRX_CHECK(!a.A1, "a two-source A (conv1x1_as_dense) needs the large-tile path");
+  // one plan per call (gemm_plan.cpp): the path, and whether it honours every feature the arguments request — the
+  // answers the gemm_* queries gave the caller
+  const GemmPlan p = gemm_plan(a);
+  IRX_CHECK(!(a.ln_rs || a.ln_part) || (a.ln_u && p.ln_fold), "folded LayerNorm needs the large-tile path");
+  IRX_CHECK(!a.geglu || p.geglu, "GEGLU epilogue needs the large-tile path");
+  IRX_CHECK((!a.ln_out || p.ln_out) && (!a.b_rows || p.bimg),
+            "LayerNorm partials / per-image weights need the large-tile epilogue");
+  IRX_CHECK(!a.gn_part || p.gn_rows > 0, "GroupNorm partials need the large-tile epilogue");
+  IRX_CHECK(!a.gn_ab || p.gn_fused, "GroupNorm-fused operand needs the halo conv path");
+  IRX_CHECK(!a.A1 || p.path == GEMM_SK || p.large(), "a two-source A (conv1x1_as_dense) needs the large-tile path");
   // the 4-wave kernel maps rows through c_off for head-split outputs only: a sub-pixel (up2) output would land at
-  // low-resolution offsets (gemm_up2_ok does not mirror every early exit of gemm_large_tile)
-  IRX_CHECK(!a.up2_w, "a per-parity upsampler conv (up2) needs the large-tile path");
-  if (const int sp = small_splits(a)) {   // raw fp32 partials per K split (the batch index), then the reduce kernel
-    GemmArgs p = a;
-    p.K = a.K / sp;
-    p.batch = sp;
-    p.sA = p.K;
-    p.sB = p.K;
-    // the caller's workspace when it gave one (the models: gemm_workspace_bytes reports these partials, so a captured
-    // graph never points into the library's scratch, which a later, larger call frees and reallocates); bare op
-    // calls fall back to that scratch
-    const size_t need = (size_t)sp * a.M * a.N * sizeof(float);
-    p.C = (a.splitk_ws && a.splitk_ws_bytes >= need) ? a.splitk_ws : (void*)splitk_scratch(need);
-    p.hs_L = 0;           // partials row-major; the reduce kernel maps head-split rows (c_off)
-    p.ldc = a.N;
-    p.sC = (long)a.M * a.N;
-    p.out_f32 = 1;
-    p.bias = nullptr;
-    p.rowadd = nullptr;
-    p.residual = nullptr;
-    p.act = ACT_NONE;
-    p.alpha = 1.f;
-    p.out_scale = 1.f;
-    if (a.dtype == F16) launch_t<f16_t>(p, s);
-    else launch_t<bf16_t>(p, s);
-    splitk_reduce(a, (const float*)p.C, sp, a.M, a.N, s);
-    return;
+  // low-resolution offsets
+  IRX_CHECK(!a.up2_w || p.up2, "a per-parity upsampler conv (up2) needs the large-tile path");
+  switch (p.path) {
+    case GEMM_SK:
+      IRX_CHECK(gemm_sk(a, s), "gemm_sk declined a call planned for it");
+      return;
+    case GEMM_HALO:
+    case GEMM_LARGE:
+      gemm_large_tile(a, p, s);
+      return;
+    case GEMM_WAVE4_SPLIT: {   // raw fp32 partials per K split (the batch index), then the reduce kernel
+      GemmArgs q = a;
+      q.K = a.K / p.splits;
+      q.batch = p.splits;
+      q.sA = q.K;
+      q.sB = q.K;
+      // the caller's workspace when it gave one (the models: gemm_workspace_bytes reports these partials, so a captured
+      // graph never points into the library's scratch, which a later, larger call frees and reallocates); bare op
+      // calls fall back to that scratch
+      q.C = (a.splitk_ws && a.splitk_ws_bytes >= p.ws_bytes) ? a.splitk_ws : (void*)splitk_scratch(p.ws_bytes);
+      q.hs_L = 0;           // partials row-major; the reduce kernel maps head-split rows (c_off)
+      q.ldc = a.N;
+      q.sC = (long)a.M * a.N;
+      q.out_f32 = 1;
+      q.bias = nullptr;
+      q.rowadd = nullptr;
+      q.residual = nullptr;
+      q.act = ACT_NONE;
+      q.alpha = 1.f;
+      q.out_scale = 1.f;
+      if (a.dtype == F16) launch_t<f16_t>(q, s);
+      else launch_t<bf16_t>(q, s);
+      splitk_reduce(a, (const float*)q.C, p.splits, p.Mp, p.Np, 1, s);
+      return;
+    }
+    default:
+      if (a.dtype == F32) launch_t<float>(a, s);
+      else if (a.dtype == F16) launch_t<f16_t>(a, s);
+      else launch_t<bf16_t>(a, s);
   }
-  if (a.dtype == F32) launch_t<float>(a, s);
-  else if (a.dtype == F16) launch_t<f16_t>(a, s);
-  else launch_t<bf16_t>(a, s);
 }
 
 }  // namespace irx

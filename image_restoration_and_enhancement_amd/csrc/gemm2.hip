@@ -16,13 +16,17 @@
 //   * XCD-aware block -> tile mapping (tiles sharing an A panel on one XCD's L2).
 // Requirements (else the 4-wave kernel in gemm.hip runs): bf16, K % 64 == 0, conv channel
 // counts % 64 == 0 (a 64-deep K step never straddles a tap or the concat seam).
+//
+// This file holds the kernels, launch2 and the launcher gemm_large_tile(), which only translates a GemmPlan into a
+// launch.  Which call takes which instantiation, K splits and tile order is decided in gemm_plan.cpp (host-only, so a
+// policy change does not recompile the kernels).
 #include <cmath>
 #include <map>
 #include <mutex>
 #include <type_traits>
 #include <utility>
 
-#include "ops.h"
+#include "gemm_plan.h"
 #include "profile.h"
 
 namespace irx {
@@ -51,8 +55,7 @@ namespace {
 typedef __attribute__((address_space(3))) void lds_void;
 
 typedef __attribute__((address_space(1))) unsigned gu32;
-constexpr int kSplitCounters = 1 << 16;
-// Split arrival tickets live in one zero-initialised array PER STREAM (self-resetting: the last arriver
+// Split arrival tickets (kSplitCounters) live in one zero-initialised array PER STREAM (self-resetting: the last arriver
 // stores 0 back).  Launches on one stream are ordered, so a stream's tickets are never shared by two
 // GEMMs in flight; two handles on two streams get disjoint arrays (no cross-stream ticket mixing).
 
@@ -105,10 +108,10 @@ __device__ __forceinline__ void glds16_s(uint32_t voff, const void* base, uint32
 // LDS once per slab and read by all 9 taps through shifted fragment addresses.  Per slab a block moves
 // one halo + 9 B panels instead of 9 A panels + 9 B panels (1.5x fewer L2 -> LDS bytes per MFMA at
 // 256x160 than the 256x320 im2col tile), with whole 128-B lines per request (BK 64).
-constexpr int kHaloWMax = 64;    // widest image row a halo tile takes (LDS: 2 x (BM + 2W) x 2BK B)
-// strip halo tiles (HALO == 5): 8 rows x 32 columns; halo 10 x 32 pixels + the neighbouring columns at halo pixels
+// (kHaloWMax, gemm_plan.h: the widest image row a halo tile takes)
+// strip halo tiles (HALO == 5): 8 rows x kStripW columns; halo 10 x 32 pixels + the neighbouring columns at halo pixels
 // kStripEdgeL + h / kStripEdgeR + h (h = halo row 0..9), inside the (BM + 2 kHaloWMax)-pixel halo buffer
-constexpr int kStripW = 32, kStripEdgeL = 320, kStripEdgeR = 336;
+constexpr int kStripEdgeL = 320, kStripEdgeR = 336;
 static_assert(kStripEdgeR + 16 <= 256 + 2 * kHaloWMax, "strip halo edge columns");
 
 template <typename T, int BM, int BN, int WM, int WN, int BK, int S, bool CONV, bool OUTF32, bool RESIZE,
@@ -1500,7 +1503,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs a, const fl
 // channel chunk (8 of them) x a row stride of 32; shifted fp32 sums of the rounded outputs -> raw fp64, folded over
 // the 32 row lanes through LDS in a fixed order (the large-tile epilogue's arithmetic; batch invariant: a row block
 // never straddles two images).
-constexpr int kRedGnRows = 64;
 template <typename T>
 __global__ __launch_bounds__(256) void splitk_reduce_gn_kernel(GemmArgs a, const float* __restrict__ ws, int splits,
                                                                int Mp, int Np) {
@@ -1603,15 +1605,7 @@ void launch2_t(const GemmArgs& a, const Split& sp, hipStream_t s) {
     splitk_reduce_gn_kernel<T><<<dim3(a.M / kRedGnRows, a.N / 64), 256, 0, s>>>(a, sp.ws, sp.splits, sp.Mp, sp.Np);
     IRX_LAUNCH_CHECK();
   } else if (sp.splits > 1 && !sp.inkernel) {
-    ProfScope ps(prof_on() ? std::string("irx::(anonymous namespace)::splitk_reduce_kernel<") + tn + ", " +
-                                 (a.out_f32 ? "true" : "false") + ">"
-                           : std::string(),
-                 0.0, s);
-    const long n = (long)a.M * (a.N / 8);
-    dim3 g2((unsigned)((n + 255) / 256), a.batch);
-    if (a.out_f32) splitk_reduce_kernel<T, true><<<g2, 256, 0, s>>>(a, sp.ws, sp.splits, sp.Mp, sp.Np);
-    else splitk_reduce_kernel<T, false><<<g2, 256, 0, s>>>(a, sp.ws, sp.splits, sp.Mp, sp.Np);
-    IRX_LAUNCH_CHECK();
+    splitk_reduce(a, sp.ws, sp.splits, sp.Mp, sp.Np, a.batch, s);
   }
 }
 
@@ -1622,82 +1616,7 @@ void launch2(const GemmArgs& a, const Split& sp, hipStream_t s) {
   else launch2_t<bf16_t, BM, BN, WM, WN, BK, S, HALO, PP>(a, sp, s);
 }
 
-// ------------------------------------------------------------------ tile / split policy
-constexpr int kCUs = 256;
-
-struct Choice {
-  int BM = 0, BN = 0, splits = 1, per = 0;
-  bool small = false;   // 4-wave block, two resident per CU (short-K GEMMs: one block's prologue/epilogue
-                        // overlaps the other's MFMA loop)
-};
-
-int step_k() { return g_gemm_deep == 1 ? 32 : 64; }   // K depth of one pipeline stage (eligibility granule)
-
-// rows (M x batch) the policy plans for: image-indexed GEMMs at kCanonImages images (batch invariance)
-long canon_rows(const GemmArgs& a) {
-  const long rows = (long)a.M * a.batch;
-  return a.imgs > 0 ? rows / a.imgs * kCanonImages : rows;
-}
-int canon_batch(const GemmArgs& a) { return (a.imgs > 0 && a.batch > 1) ? kCanonImages : a.batch; }
-
-Choice choose(const GemmArgs& a) {
-  Choice best;
-  const int nk = a.K / step_k();
-  if (g_gemm_small && g_gemm_deep == 0 && a.K <= g_gemm_small_kmax) {
-    const int bn = (!a.geglu && a.N % 160 == 0) ? 160 : (a.N % 128 == 0 ? 128 : 0);
-    if (bn) {
-      best.BM = 128; best.BN = bn; best.small = true; best.splits = 1; best.per = nk;
-      return best;
-    }
-  }
-  if (g_gemm_force > 0 && g_gemm_deep == 0) {   // tuning sweeps: BM*100000 + BN*100 + splits
-    const int BM = g_gemm_force / 100000, BN = (g_gemm_force / 100) % 1000, sp = g_gemm_force % 100;
-    const bool ok = (BM == 256 || BM == 128 || (BM == 64 && BN == 320 && sp == 1 && !a.gn_part)) &&
-                    (BN == 320 || BN == 256 || BN == 128) && a.N % BN == 0 &&
-                    sp >= 1 && (sp == 1 || !((a.out_f32 && canon_batch(a) > 1) || a.geglu)) && (!a.geglu || BN % 128 == 0);
-    if (ok) {
-      best.BM = BM; best.BN = BN; best.splits = sp; best.per = (nk + sp - 1) / sp;
-      if ((long)(sp - 1) * best.per < nk) return best;
-    }
-    best = Choice();
-  }
-  double best_score = -1.0;
-  const int cands[7][2] = {{256, 320}, {256, 256}, {128, 320}, {256, 128}, {128, 256}, {128, 128}, {256, 160}};
-  for (auto& c : cands) {
-    const int BM = c[0], BN = c[1];
-    if (BN == 160 && g_gemm_deep != 2) continue;
-    if (BN == 320 && BM == 256 && (g_gemm_deep != 0 || !g_tile_256x320)) continue;
-    if (a.N % BN != 0) continue;
-    if (a.geglu && BN % 128 != 0) continue;      // tiles must hold whole (value, gate) block pairs
-    const long tiles = (canon_rows(a) + BM - 1) / BM * (a.N / BN);
-    // per-tile efficiency at full occupancy, calibrated on the batch-16 UNet / batch-8 VAE shapes
-    // (scripts/gemm_sweep.py): the load path (L2 -> LDS-DMA) bounds the small tiles, 128x128 keeps two
-    // blocks per CU resident (its prologue / epilogue overlap the other block's loop), 256x128 (4x2 waves)
-    // loses to it everywhere measured
-    const double eff = BM == 256 ? (BN >= 256 ? 1.0 : BN == 160 ? 0.9 : 0.65)
-                                 : (BN == 320 ? 0.97 : BN == 256 ? 0.75 : 0.78);
-    const int resident = (BM == 128 && BN == 128 && g_gemm_deep == 0) ? 2 : 1;
-    const long cap = (long)kCUs * resident;
-    for (int splits = 1; splits <= 8; splits *= 2) {
-      if (splits > 1 && ((a.out_f32 && canon_batch(a) > 1) || a.geglu)) break;
-      const int per = (nk + splits - 1) / splits;
-      if (per * step_k() < 512 && splits > 1) break;    // keep >= 512 of K per split
-      if ((long)(splits - 1) * per >= nk) break;        // no empty split
-      const long blocks = tiles * splits;
-      const double util = (double)blocks / ((double)((blocks + cap - 1) / cap) * cap);
-      // split-K pays an fp32 partial write + read per split and a reduction tail, relatively more when
-      // each split is short
-      const double cost_split = splits > 1 ? (1.0 + 0.35 * std::log2((double)splits)) * (per < 16 ? 1.6 : 1.0) : 1.0;
-      const double score = util * eff / cost_split;
-      if (score > best_score + 1e-9) {
-        best_score = score;
-        best.BM = BM; best.BN = BN; best.splits = splits; best.per = per;
-      }
-    }
-  }
-  return best;
-}
-
+// ------------------------------------------------------------------ per-stream tickets, scratch fallback
 std::mutex g_ws_mu;
 std::map<hipStream_t, unsigned*> g_cnt;   // per-stream split-K tickets (never freed: 256 KiB per stream)
 
@@ -1725,123 +1644,24 @@ float* internal_ws(size_t bytes) {
   return g_ws;
 }
 
-bool vec_ok(const GemmArgs& a) {
-  return !a.out_f32 && a.N % 8 == 0 && a.ldc % 8 == 0 && ((uintptr_t)a.C % 16) == 0 &&
-         (!a.residual || (a.ldr % 8 == 0 && ((uintptr_t)a.residual % 16) == 0)) &&
-         (a.batch == 1 || (a.sC % 8 == 0 && (!a.residual || a.sR % 8 == 0)));
-}
-
-bool eligible(const GemmArgs& a) {
-  const int bk = step_k();
-  if (!(g_large_mask & (a.conv ? 2 : 1))) return false;   // (A/B: large tiles for dense GEMMs / convs only)
-  if (!a.conv && g_large_dense != 63) {   // (diagnostics: dense classes on large tiles)
-    const int cls = a.geglu ? (a.K <= 320 ? 4 : a.K <= 640 ? 16 : 32) : a.hs_L ? 2 : a.N <= 1280 ? 1 : 8;
-    if (!(g_large_dense & cls)) return false;
-  }
-  if (a.hs_L && !vec_ok(a)) return false;  // head-split stores: the 16-byte LDS-staged epilogue only
-  if (a.act != ACT_NONE) return false;   // activations are fused by the 4-wave kernel only (tiny GEMMs)
-  // the unrolled scalar (non-16-byte) epilogue only scales and adds bias: row add / residual need vec rows
-  if (!vec_ok(a) && (a.rowadd || a.residual)) return false;
-  if (a.rowadd && (a.rowadd_ld % 4 != 0 || ((uintptr_t)a.rowadd % 16) != 0)) return false;
-  if (!is16(a.dtype) || a.K % bk != 0 || a.ldb % 8 != 0) return false;
-  if (canon_rows(a) < 512) return false;           // tiny outputs: the 64x64 4-wave tiles waste less
-  if (a.geglu && (a.out_f32 || a.residual || a.batch != 1 || a.N % 128 != 0)) return false;
-  if (a.conv) return !a.out_f32 && a.g.C0 % bk == 0 && a.g.C1 % bk == 0;
-  if (a.A1 && (a.batch != 1 || a.kA1 % 64 != 0 || a.lda1 % 8 != 0 || ((uintptr_t)a.A1 % 16) != 0)) return false;
-  return a.lda % 8 == 0 && (a.batch == 1 || a.sA % 8 == 0);
-}
-
-
 }  // namespace
 
-int g_large_dense = 63;  // irx_set_option("large_dense", m): dense classes on large tiles: 1 N <= 1280, 2 head-split,
-                         // GEGLU at K 4: 320, 16: 640, 32: >= 1280, 8 other
-int g_gemm_nmajor = 1;
-int g_large_mask = 3;  // irx_set_option("large_mask", m): bit 0 dense GEMMs, bit 1 convs take the large tiles
-int g_gemm_deep = 0;   // irx_set_option("gemm_deep", m): 0 two-stage BK 64, 1 BK-32 ring, 2 BK-64 3/4-stage ring
 int g_gemm_dbg = 0;
-bool g_gemm_small = false;   // irx_set_option("gemm_small", 1): 4-wave 128x160 / 128x128 tiles for K <= kmax
-int g_gemm_small_kmax = 1280;
-bool g_splitk_inkernel = true;   // irx_set_option("splitk_inkernel", 0): separate split-K reduce kernel (A/B)
-bool g_tile_256x320 = true;      // irx_set_option("tile_256x320", 0): no 256x320 tiles (A/B)
-int g_conv_halo = 1;             // irx_set_option("conv_halo", m): 0 im2col walk for every conv (A/B),
-                                 // 1 halo tiles where the grid fills the chip, 2 wherever they fit (tests)
-int g_gemm_force = 0;            // irx_set_option("gemm_force", BM*100000 + BN*100 + splits): tuning sweeps
 
-int g_gn_fuse = 0;   // measured slower: the halo normalisation's VALU work does not hide under the MFMAs
-int halo_bn(const GemmArgs& a);
-
-int halo_mode(const GemmArgs& a);
-int halo_split_count(const GemmArgs& a, int hbn);
-
-bool gemm_gn_fusable(const GemmArgs& a) {   // (the lock-step halo loop, HALO == 1: 160-wide row tiles only)
-  return g_gn_fuse && g_large_tiles && is16(a.dtype) && eligible(a) && halo_bn(a) == 160 && halo_mode(a) == 1;
-}
-
-int g_conv1x1_dense = 1;   // irx_set_option("conv1x1_dense", 0): 1x1 convs on the im2col conv path (A/B)
-
-bool conv1x1_as_dense(GemmArgs& a) {
-  const ConvGeom& g = a.g;
-  if (!g_conv1x1_dense || !a.conv || !is16(a.dtype) || a.batch != 1 || a.gn_ab || a.up2_w || a.act != ACT_NONE) return false;
-  if (g.KH != 1 || g.KW != 1 || g.stride != 1 || g.pad_t != 0 || g.pad_l != 0) return false;
-  if (g.Hv != g.Hin || g.Wv != g.Win || g.Ho != g.Hin || g.Wo != g.Win) return false;
-  GemmArgs d = a;
-  d.conv = 0;
-  d.g = ConvGeom();
-  d.A = g.src0; d.lda = g.C0;
-  d.A1 = g.C1 ? g.src1 : nullptr; d.lda1 = g.C1; d.kA1 = g.C1 ? g.C0 : 0;
-  if (!g_large_tiles || !eligible(d) || choose(d).BM == 0) return false;
-  a = d;
-  return true;
-}
-
-int g_gn_parts = 1;
-int g_gn_red_parts = 1;   // irx_set_option("gn_red_parts", 0): split-K reduce kernels do not emit GroupNorm partials (A/B)
-
-int gemm_emits_gn_parts(const GemmArgs& a) {
-  if (!g_gn_parts || !g_large_tiles || !is16(a.dtype) || !eligible(a) || !vec_ok(a)) return 0;
-  if (a.geglu || a.hs_L || a.batch != 1 || a.out_f32) return 0;
-  if (halo_bn(a)) {
-    if (halo_mode(a) == 3)   // (8x8 images, K splits reduced by splitk_reduce_gn_kernel: one partial per image)
-      return (g_gn_red_parts && !a.up2_w && halo_split_count(a, 160) > 1 && a.M % kRedGnRows == 0 && a.N % 64 == 0 && a.act == ACT_NONE && !a.b_rows) ? kRedGnRows
-                                                                                                            : 0;
-    return a.M % 256 == 0 ? 256 : 0;
-  }
-  const Choice c = choose(a);
-  if (c.BM == 0) return 0;
-  if (c.splits > 1) {   // the in-kernel split-K reduction runs the epilogue; the separate reduce kernel emits them too
-    const long tiles = (long)((a.M + c.BM - 1) / c.BM) * ((a.N + c.BN - 1) / c.BN);
-    if (!(g_splitk_inkernel && c.splits == 2 && tiles <= kSplitCounters))   // splitk_reduce_gn_kernel
-      // (splitk_reduce_gn_kernel applies one bias vector and assumes the plain m * ldc layout: no per-image
-      // weights / bias)
-      return (g_gn_red_parts && !a.up2_w && !a.b_rows && !c.small && c.BM != 64 && a.M % kRedGnRows == 0 && a.N % 64 == 0 && a.act == ACT_NONE)
-                 ? kRedGnRows : 0;
-  }
-  if (a.up2_w && ((long)a.up2_h * a.up2_w) % c.BM) return 0;   // (a sub-pixel tile's rows in one image)
-  return a.M % c.BM ? 0 : c.BM;
-}
-
-bool gemm_up2_ok(const GemmArgs& a) {
-  // every store of the large-tile path goes through c_off (the 16-byte epilogue, the split-K reduce kernel); the
-  // scalar epilogue and the 4-wave kernel do not map rows
-  // (the halo parity convs, HALO == 6 / 7, store through c_off too)
-  return g_large_tiles && eligible(a) && vec_ok(a) && a.batch == 1 && !a.hs_L &&
-         (halo_bn(a) || (!gemm_sk_eligible(a) && choose(a).BM != 0));
-}
-
-// Split-K partials of the 4-wave kernel (gemm.hip, small-M GEMMs) reduced with the large-tile path's kernel: the
-// same fp32 sums over the splits in order, then alpha / bias / row add / activation / residual / output scale
 float* splitk_scratch(size_t bytes) { return internal_ws(bytes); }
 
-void splitk_reduce(const GemmArgs& a, const float* ws, int splits, int Mp, int Np, hipStream_t s) {
-  IRX_CHECK(a.N % 8 == 0 && a.batch == 1 && is16(a.dtype), "splitk_reduce: 16-bit, N % 8 == 0, batch 1");
+// Split-K partials ws [batch * splits][Mp][Np] reduced into C: the fp32 sums over the splits in order, then alpha /
+// bias / row add / activation / residual / output scale.  The large-tile path's splits that do not reduce in the
+// kernel, and the 4-wave kernel's small-M splits (gemm.hip)
+void splitk_reduce(const GemmArgs& a, const float* ws, int splits, int Mp, int Np, int batch, hipStream_t s) {
+  IRX_CHECK(a.N % 8 == 0 && is16(a.dtype), "splitk_reduce: 16-bit, N % 8 == 0");
   const char* tn = a.dtype == F16 ? "_Float16" : "unsigned short";
   ProfScope ps(prof_on() ? std::string("irx::(anonymous namespace)::splitk_reduce_kernel<") + tn + ", " +
                                (a.out_f32 ? "true" : "false") + ">"
                          : std::string(),
                0.0, s);
   const long n = (long)a.M * (a.N / 8);
-  const dim3 g2((unsigned)((n + 255) / 256), 1);
+  const dim3 g2((unsigned)((n + 255) / 256), batch);
   if (a.dtype == F16) {
     if (a.out_f32) splitk_reduce_kernel<f16_t, true><<<g2, 256, 0, s>>>(a, ws, splits, Mp, Np);
     else splitk_reduce_kernel<f16_t, false><<<g2, 256, 0, s>>>(a, ws, splits, Mp, Np);
@@ -1852,368 +1672,76 @@ void splitk_reduce(const GemmArgs& a, const float* ws, int splits, int Mp, int N
   IRX_LAUNCH_CHECK();
 }
 
-int g_gemm_pp_chain = 1;   // irx_set_option("gemm_pp_chain", 0): the two-source 1x1 chains on the two-stage loop (A/B)
-
-int g_ln_fold = 1;
-
-bool gemm_ln_foldable(const GemmArgs& a) {
-  if (!g_large_tiles || !is16(a.dtype) || a.conv || a.alpha != 1.f || a.out_f32 || a.batch != 1) return false;
-  if (!eligible(a) || !vec_ok(a)) return false;
-  const Choice c = choose(a);
-  if (c.BM == 0) return false;
-  if (c.splits > 1) {   // only the in-kernel reduction runs the full epilogue
-    const long tiles = (long)((a.M + c.BM - 1) / c.BM) * ((a.N + c.BN - 1) / c.BN);
-    if (!(g_splitk_inkernel && c.splits == 2 && tiles <= kSplitCounters)) return false;
-  }
-  return true;
-}
-
-int g_ln_parts = 1;
-
-// The epilogue can emit LayerNorm partials (GemmArgs::ln_out): dense 16-bit large-tile GEMMs whose tiles are 320
-// columns wide (the 64x64 / 32x32-level transformer projections), run by the large-tile kernel's staged epilogue
-bool gemm_emits_ln_parts(const GemmArgs& a) {
-  if (!g_ln_parts || !g_large_tiles || !is16(a.dtype) || a.conv || a.geglu || a.hs_L || a.batch != 1 || a.out_f32) return false;
-  if (a.gn_part || a.N % kLnGroup != 0 || !eligible(a) || !vec_ok(a) || gemm_sk_eligible(a)) return false;
-  if (a.ln_out_rs && a.N != kLnGroup) return false;
-  const Choice c = choose(a);
-  if (c.BN != kLnGroup || c.small || (c.BM != 256 && c.BM != 128)) return false;
-  if (c.splits > 1) {   // only the in-kernel reduction runs the full epilogue
-    const long tiles = (long)((a.M + c.BM - 1) / c.BM) * ((a.N + c.BN - 1) / c.BN);
-    if (!(g_splitk_inkernel && c.splits == 2 && tiles <= kSplitCounters)) return false;
-  }
-  return g_gemm_pp != 1 && g_gemm_deep == 0;
-}
-
-int g_gn_fold = 1;
-
-// Per-image B / bias (GemmArgs::b_rows): dense 16-bit large tiles whose row tiles never straddle two images
-bool gemm_bimg_ok(const GemmArgs& a) {
-  if (!g_large_tiles || !is16(a.dtype) || a.conv || a.geglu || a.batch != 1 || a.out_f32 || a.b_rows <= 0) return false;
-  if (a.M % a.b_rows || !eligible(a) || !vec_ok(a) || gemm_sk_eligible(a)) return false;
-  const Choice c = choose(a);
-  if (c.BM == 0 || c.small || a.b_rows % c.BM) return false;
-  if (c.splits > 1) {   // partial sums of one tile share one image's weights; the reduce kernel indexes the bias by row
-    const long tiles = (long)((a.M + c.BM - 1) / c.BM) * ((a.N + c.BN - 1) / c.BN);
-    if (!(g_splitk_inkernel && c.splits == 2 && tiles <= kSplitCounters)) return false;
-  }
-  return g_gemm_pp != 1 && g_gemm_deep == 0;
-}
-
-int halo_splits(const GemmArgs& a, long tiles);
-
-// K splits the large-tile path would run `a` with (1: none; 0: not a large-tile shape) — for tests / diagnostics
-int gemm_large_splits(const GemmArgs& a) {
-  if (!g_large_tiles || !eligible(a) || gemm_sk_eligible(a)) return 0;
-  if (const int hbn = halo_bn(a)) return halo_split_count(a, hbn);
-  const Choice c = choose(a);
-  return c.BM ? c.splits : 0;
-}
-
-bool gemm_geglu_fusable(const GemmArgs& a) {
-  if (!g_large_tiles || !a.geglu || !eligible(a) || !vec_ok(a)) return false;
-  if (gemm_sk_eligible(a)) return true;
-  // (round 3 kept partial per-image row tiles unfused after an fp16 batch dependence; its cause was hipcc fusing the
-  // folded-LayerNorm FMA with the fp16 conversion into v_fma_mixlo_f16 at some unrolled sites only — fixed in
-  // irx_common.h f16_src, tests/test_ln_parts_gpu.py::test_ln_fold_geglu_fp16_batch_invariant)
-  return choose(a).BM != 0;
-}
-
-int halo_bn(const GemmArgs& a);
-
-int halo_splits(const GemmArgs& a, long tiles);
-
-// Tile order of a halo conv (GemmArgs::group_m; scheduling only, no numeric effect).  One XCD runs q = tiles / 8
-// consecutive logical tiles at once; in the M-major order they are q / tiles_n M tiles x all tiles_n N tiles, so at
-// the 16x16 level (16 M tiles x 8 N tiles of a 1280-channel conv, 29.5 MB of weights) every XCD streams all of B.
-// Grouped by g M tiles the range is g x q / g: per XCD ~ g halo slabs of A + q / g B panels (bytes (BM + 2W) Cin 2
-// and BN K 2).  g minimises that sum; 0 keeps the M-major order when it is within 10 % of the best.
-int g_halo_group = 1;   // irx_set_option("halo_group", 0): M-major halo tile order (A/B)
-int halo_group_m(const GemmArgs& a, int bn) {
-  if (!g_halo_group) return 0;
-  const long tiles_m = (a.M + 255) / 256, tiles_n = a.N / bn;
-  if (tiles_n < 2) return 0;
-  // logical tiles per XCD (xcd_remap ranges), of which one block per CU = 32 run at a time
-  const long q = (tiles_m * tiles_n + 7) / 8, w = std::min(q, 32L);
-  const double hpix = halo_mode(a) == 2 ? 10.0 * (kStripW + 2) : 256.0 + 2.0 * a.g.Wo;   // halo pixels per tile
-  const double a_m = hpix * (a.g.C0 + a.g.C1) * 2.0, b_n = (double)bn * a.K * 2.0;
-  auto cost = [&](long g) {   // A + B bytes of one XCD's w co-resident tiles in groups of g M tiles
-    const bool whole = w >= g * tiles_n;   // (the window spans whole groups: w / tiles_n M tiles x every N tile)
-    const long gm = whole ? (w + tiles_n - 1) / tiles_n : std::min(g, w);
-    const long gn = whole ? tiles_n : (w + g - 1) / g;
-    return gm * a_m + gn * b_n;
-  };
-  const double legacy = cost(std::max(1L, (w + tiles_n - 1) / tiles_n));   // M-major: w / tiles_n whole M rows
-  long best_g = 0;
-  double best = legacy;
-  for (long g = 1; g <= tiles_m; g *= 2)
-    if (cost(g) < best) { best = cost(g); best_g = g; }
-  return best < 0.9 * legacy ? (int)best_g : 0;
-}
-
-// Tile order of a dense large-tile GEMM (scheduling only): the cost model of halo_group_m with A panel BM x K and B
-// panel BN x K, over the 32 x `resident` tiles one XCD runs at once; 0 keeps the M-major / N-major order when the
-// grouped one is not > 10 % better.  (The GEGLU projections at 32^2 / 16^2: every XCD streamed the whole 6.5 / 26 MB
-// weight in the M-major / N-major orders.)
-int g_gemm_group = 1;   // irx_set_option("gemm_group", 0): the M-major / N-major dense tile orders only (A/B)
-int dense_group_m(const GemmArgs& a, int bm, int bn, int resident, bool nmajor) {
-  if (!g_gemm_group) return 0;
-  const long tiles_m = (a.M + bm - 1) / bm, tiles_n = (a.N + bn - 1) / bn;
-  if (tiles_n < 2 || tiles_m < 2) return 0;
-  const long q = (tiles_m * tiles_n + 7) / 8, w = std::min(q, 32L * resident);
-  const double a_m = (double)bm * a.K * 2.0, b_n = (double)bn * a.K * 2.0;
-  auto cost = [&](long g) {
-    const bool whole = w >= g * tiles_n;
-    const long gm = whole ? (w + tiles_n - 1) / tiles_n : std::min(g, w);
-    const long gn = whole ? tiles_n : (w + g - 1) / g;
-    return gm * a_m + gn * b_n;
-  };
-  // the current order: M-major = groups of one whole M row block; N-major = a window of w M tiles x w / tiles_m N tiles
-  const double legacy = nmajor ? std::min(w, tiles_m) * a_m + (double)((w + tiles_m - 1) / tiles_m) * b_n
-                               : cost(std::max(1L, (w + tiles_n - 1) / tiles_n));
-  long best_g = 0;
-  double best = legacy;
-  for (long g = 1; g <= tiles_m; g *= 2)
-    if (cost(g) < best) { best = cost(g); best_g = g; }
-  return best < 0.9 * legacy ? (int)best_g : 0;
-}
-
-size_t gemm_workspace_bytes(const GemmArgs& a) {
-  // the 4-wave kernel's small-M K splits (gemm.hip), should the large-tile path decline the call
-  const size_t small = gemm_small_split_bytes(a);
-  if (!g_large_tiles || !eligible(a)) return small;
-  if (const int hbn = halo_bn(a)) {
-    const int sp = halo_split_count(a, hbn);
-    return sp > 1 ? (size_t)sp * ((a.M + 255) / 256 * 256) * a.N * sizeof(float) : 0;
-  }
-  const Choice c = choose(a);
-  if (c.BM == 0 || c.splits <= 1) return small;
-  return std::max(small, (size_t)c.splits * a.batch * ((a.M + c.BM - 1) / c.BM * c.BM) *
-                             ((a.N + c.BN - 1) / c.BN * c.BN) * sizeof(float));
-}
-
-// K splits of a halo conv (whole 64-channel slabs per split): 1 when the tiles fill the chip, 2 (in-kernel
-// reduction) when two splits do, 0 = the halo path does not take the shape.
-int g_halo_split = 1;   // irx_set_option("halo_split", 0): no K-split halo tiles (A/B)
-int g_halo_pipe = 1;    // irx_set_option("halo_pipe", 0): the round-2 halo main loop (A/B)
-// irx_set_option("gemm_pp", m): ping-pong main loops.  2 (default): the lean dense form on 256x256 tiles only (the
-// 32x32 / 16x16-level GEGLU projections: ff1 -12 / -14 % at the kbench shapes, 49.9 -> 46.5 ms/step in the bench;
-// profiles/r04_kbench_gemm_pp_lean.txt); 1: every dense / im2col tile (the im2col convs keep the round-3 branchy form,
-// which is slower there, and the lean form loses at 128x128 / 1280-wide 16x16 shapes); 3: 256x256 + 256x320 (measured
-// 513.7 vs 508.2 ms/step: off); 0: none
-int g_gemm_pp = 2;
-
-int halo_splits(const GemmArgs& a, long tiles) {
-  if (tiles >= kCUs || g_conv_halo >= 2) return 1;
-  if (!g_halo_split) return 0;
-  const int slabs = (a.g.C0 + a.g.C1) / 64;
-  if (g_splitk_inkernel && 2 * tiles >= kCUs && slabs >= 8 && tiles <= kSplitCounters) return 2;
-  return 0;
-}
-
-// irx_set_option("halo_strip", m): 0 no strip tiles (VAE / 768^2 convs on the im2col walk, A/B), 1 (default) strip
-// tiles where whole-row tiles do not fit (W > 64 or no power of two), 2 strip tiles wherever the shape allows (tests:
-// strips == rows bit for bit at W <= 64)
-int g_halo_strip = 1;
-int g_halo_up2 = 1;   // irx_set_option("halo_up2", 0): upsampler parity convs on the im2col walk (A/B)
-int g_halo_mi = 1;    // irx_set_option("halo_mi", 0): the 8x8-level convs on the im2col walk (A/B)
-
-// Halo tile mode of a 3x3 / stride-1 / pad-1 conv, or of one parity's 2x2 conv of a nearest-2x upsampler
-// (GemmArgs::up2_*, pad (1 - a, 1 - b)): 1 = 256-pixel tiles of whole image rows (W in {16, 32, 64}), 2 = 8 x 32
-// strip tiles (W % 32 == 0, H % 8 == 0; HALO == 5 / 7), 0 = neither.  The decision does not depend on the parity.
-int halo_mode(const GemmArgs& a) {
-  const ConvGeom& g = a.g;
-  if (!g_conv_halo || !a.conv || a.batch != 1 || a.geglu || a.out_f32 || !vec_ok(a)) return 0;
-  if (g.stride != 1) return 0;
-  if (a.up2_w) {   // (ping-pong loop only)
-    if (!g_halo_up2 || !g_halo_pipe || a.gn_ab || g.KH != 2 || g.KW != 2 || (g.pad_t & ~1) || (g.pad_l & ~1)) return 0;
-  } else if (g.KH != 3 || g.KW != 3 || g.pad_t != 1 || g.pad_l != 1) {
-    return 0;
-  }
-  if (g.Hv != g.Hin || g.Wv != g.Win || g.Ho != g.Hin || g.Wo != g.Win) return 0;
-  if (g.C0 % 64 || g.C1 % 64 || g.C0 <= 0) return 0;
-  const int W = g.Win;
-  if ((long)g.N * g.Hin * W != a.M) return 0;
-  // 3 = four whole 8x8 images per tile (HALO == 8): any image count (a partial last tile), so the choice is
-  // batch-invariant like the others
-  if (W == 8 && g.Hin == 8 && g_halo_mi && g_halo_pipe && !a.gn_ab && a.M % 64 == 0) return 3;
-  // (parity convs on row / strip tiles: whole 256-row tiles of one image, the sub-pixel GroupNorm partial blocks)
-  if (a.up2_w && ((long)a.up2_h * a.up2_w) % 256) return 0;
-  if (a.M % 256) return 0;
-  const bool rows = W >= 16 && W <= kHaloWMax && !(W & (W - 1)) && 256 % W == 0 && g.Hin % (256 / W) == 0;
-  // (strips: the ping-pong loop only, no GroupNorm-fused operand)
-  const bool strips = g_halo_strip && g_halo_pipe && !a.gn_ab && W % kStripW == 0 && g.Hin % (256 / kStripW) == 0;
-  if (strips && (g_halo_strip == 2 || !rows)) return 2;
-  return rows ? 1 : 0;
-}
-
-// Halo tile (BN) for a 3x3 / stride-1 / pad-1 conv on halo tiles (halo_mode) whose grid fills the chip (alone or with
-// two K splits); 0 = not applicable.  BN 160 (UNet widths), else 128 (VAE widths 128 / 256 / 512; ping-pong loop only)
-int halo_bn(const GemmArgs& a) {
-  const int mode = halo_mode(a);
-  if (!mode) return 0;
-  const int bn = a.N % 160 == 0 ? 160 : (a.N % 128 == 0 && g_halo_pipe && !a.gn_ab) ? 128 : 0;
-  if (mode == 3) return bn == 160 ? 160 : 0;   // (HALO == 8 instantiated at BN 160: the UNet's 1280 channels)
-  if (!bn || !halo_splits(a, canon_rows(a) / 256 * (a.N / bn))) return 0;
-  if (a.up2_w && mode == 2 && bn != 128) return 0;   // (strip parity convs: the VAE widths only, HALO == 7 at BN 128)
-  // (GroupNorm-fused operand: one 512-element chunk of the (256 + 2W) x 8 halo per tap, taps 3..8)
-  static_assert((256 + 2 * kHaloWMax) * 8 <= 512 * 6, "halo normalisation chunks");
-  return bn;
-}
-
-// K splits of a halo conv: halo_splits (1 or 2, in-kernel reduction), or for the 8x8 images (mode 3) whole slabs per
-// split for about one block per CU (the canonical 16 images: 4 row tiles x N / 160), reduced by the separate kernel
-int halo_split_count(const GemmArgs& a, int hbn) {
-  if (halo_mode(a) != 3) return halo_splits(a, canon_rows(a) / 256 * (a.N / hbn));
-  const long tiles = (canon_rows(a) + 255) / 256 * (a.N / hbn);
-  const int slabs = (a.g.C0 + a.g.C1) / 64;
-  const int want = (int)std::max(1L, std::min(8L, (long)kCUs / std::max(1L, tiles)));
-  const int per = (slabs + want - 1) / want;
-  return (slabs + per - 1) / per;
-}
-
-// Returns false (caller uses the 4-wave kernel) when the shape does not fit the large-tile path.
-bool gemm_large_tile(const GemmArgs& a, hipStream_t s) {
-  if (!eligible(a)) return false;
-  IRX_CHECK(!a.gn_ab || halo_bn(a), "GroupNorm-fused operand needs the halo conv path");
-  IRX_CHECK(!a.gn_part || gemm_emits_gn_parts(a), "GroupNorm partials need the large-tile epilogue");
-  IRX_CHECK(!(a.ln_rs || a.ln_part) || gemm_ln_foldable(a), "folded LayerNorm needs the large-tile epilogue");
-  IRX_CHECK(!a.ln_out || gemm_emits_ln_parts(a), "LayerNorm partials need the large-tile epilogue");
-  IRX_CHECK(!a.b_rows || gemm_bimg_ok(a), "per-image weights need the large-tile path");
-  if (gemm_sk(a, s)) return true;   // K = 320 streaming path (gemm_sk.hip)
-  if (const int hbn = halo_bn(a)) {
-    GemmArgs b = a;
-    b.vec_epilogue = 1;
-    b.dbg = g_gemm_dbg;
-    b.group_m = halo_group_m(a, hbn);
-    Split sp;
-    sp.per = a.K / 64;
-    const int splits = halo_split_count(a, hbn);
-    const int ntap = a.up2_w ? 4 : 9;
-    const bool mi = halo_mode(a) == 3;
-    if (splits > 1) {   // whole slabs per split, in-kernel last-arriver reduction (fp32 partials; 8x8: reduce kernel)
-      const int slabs = (a.g.C0 + a.g.C1) / 64;
-      sp.splits = splits;
-      sp.per = ntap * ((slabs + splits - 1) / splits);
-      sp.Mp = (a.M + 255) / 256 * 256;   // (whole row tiles of partials: a partial last tile stores all its rows)
-      sp.Np = a.N;
-      const size_t need = (size_t)splits * sp.Mp * a.N * sizeof(float);
-      sp.ws = (a.splitk_ws && a.splitk_ws_bytes >= need) ? (float*)a.splitk_ws : internal_ws(need);
-      sp.inkernel = !mi;
-      if (sp.inkernel) sp.cnt = stream_counters(s);
-    }
-#ifdef IRX_HALO_DIAG
-    if (g_halo_pipe && !a.gn_ab && b.dbg && a.dtype == BF16) launch2<256, 160, 4, 2, 64, 3, 4>(b, sp, s);   // (diagnostics)
-    else
-#endif
-    if (mi) {                           // four 8x8 images per tile (parity convs: 4 taps)
-      if (a.up2_w) launch2<256, 160, 4, 2, 64, 3, 9>(b, sp, s);
-      else launch2<256, 160, 4, 2, 64, 3, 8>(b, sp, s);
-    } else if (a.up2_w) {               // upsampler parity convs: 4 taps per slab
-      if (halo_mode(a) == 2) launch2<256, 128, 4, 2, 64, 3, 7>(b, sp, s);
-      else if (hbn == 160) launch2<256, 160, 4, 2, 64, 3, 6>(b, sp, s);
-      else launch2<256, 128, 4, 2, 64, 3, 6>(b, sp, s);
-    } else if (halo_mode(a) == 2) {     // strip tiles (ping-pong main loop)
-      if (hbn == 160) launch2<256, 160, 4, 2, 64, 3, 5>(b, sp, s);
-      else launch2<256, 128, 4, 2, 64, 3, 5>(b, sp, s);
-    } else if (g_halo_pipe && !a.gn_ab) {   // ping-pong main loop
-      if (hbn == 160) launch2<256, 160, 4, 2, 64, 3, 2>(b, sp, s);
-      else launch2<256, 128, 4, 2, 64, 3, 2>(b, sp, s);
-    } else {
-      launch2<256, 160, 4, 2, 64, 3, 1>(b, sp, s);
-    }
-    return true;
-  }
-  const Choice c = choose(a);
-  if (c.BM == 0) return false;
+// Launches a GEMM_HALO / GEMM_LARGE plan (gemm_plan.cpp decides; nothing is decided here)
+void gemm_large_tile(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+  IRX_CHECK(p.large(), "gemm_large_tile: not a large-tile plan");
   GemmArgs b = a;
-  b.vec_epilogue = vec_ok(a);
+  b.vec_epilogue = p.vec_epilogue;
   b.dbg = g_gemm_dbg;
-  // tile order (scheduling only, no numeric effect): N-major when the weights outweigh the activation rows, so that an
-  // XCD's consecutive tiles re-use one B panel from its L2 instead of every XCD streaming all of B
-  b.nmajor = g_gemm_nmajor == 2 || (g_gemm_nmajor == 1 && (long)a.N * a.batch > (long)a.M * a.batch);
-  if (a.batch == 1 && !a.hs_L) {   // grouped order where it cuts an XCD's co-resident A + B bytes (GemmArgs::group_m)
-    b.group_m = dense_group_m(a, c.BM, c.BN, (c.BM == 128 && c.BN == 128) || c.small ? 2 : 1, b.nmajor);
-    if (b.group_m) b.nmajor = 0;
-  }
-  if (a.geglu && !b.vec_epilogue) return false;
+  b.nmajor = p.nmajor;
+  b.group_m = p.group_m;
   Split sp;
-  sp.splits = c.splits;
-  sp.per = c.per;
-  if (c.splits > 1) {
-    if (!b.vec_epilogue && !a.out_f32) return false;     // reduce kernel needs 16-byte output rows
-    if (a.out_f32 && (a.ldc % 8 != 0 || a.N % 8 != 0)) return false;
-    sp.Mp = (a.M + c.BM - 1) / c.BM * c.BM;
-    sp.Np = (a.N + c.BN - 1) / c.BN * c.BN;
-    const size_t need = (size_t)c.splits * a.batch * sp.Mp * sp.Np * sizeof(float);
-    sp.ws = (a.splitk_ws && a.splitk_ws_bytes >= need) ? (float*)a.splitk_ws : internal_ws(need);
-    const long tiles = (long)((a.M + c.BM - 1) / c.BM) * ((a.N + c.BN - 1) / c.BN) * a.batch;
-    // in-kernel reduction wins at 2 splits; with more, the serial last-arriver tail loses to the reduce kernel
-    sp.inkernel = g_splitk_inkernel && c.splits == 2 && tiles <= kSplitCounters;
+  sp.splits = p.splits;
+  sp.per = p.per;
+  if (p.splits > 1) {
+    sp.Mp = p.Mp;
+    sp.Np = p.Np;
+    // the caller's workspace when it gave one (gemm_workspace_bytes), else the library's scratch
+    sp.ws = (a.splitk_ws && a.splitk_ws_bytes >= p.ws_bytes) ? (float*)a.splitk_ws : internal_ws(p.ws_bytes);
+    sp.inkernel = p.inkernel;
     if (sp.inkernel) sp.cnt = stream_counters(s);
-  } else {
-    sp.per = a.K / step_k();
   }
-  if (c.BM == 64) {   // 64x320, 4 waves, BK 32, two stages (48 KiB of LDS: three blocks per CU)
-    sp.per = a.K / 32;
-    launch2<64, 320, 1, 4, 32, 2>(b, sp, s);
-    return true;
+#ifdef IRX_HALO_DIAG
+  if (p.path == GEMM_HALO && g_halo_pipe && !a.gn_ab && b.dbg && a.dtype == BF16) {   // (diagnostics)
+    launch2<256, 160, 4, 2, 64, 3, 4>(b, sp, s);
+    return;
   }
-  if (c.small) {
-    if (c.BN == 160) launch2<128, 160, 2, 2, 64, 2>(b, sp, s);
-    else launch2<128, 128, 2, 2, 64, 2>(b, sp, s);
-  } else if (g_gemm_deep == 0 &&
-             (!a.A1 || g_gemm_pp_chain) &&   // (two-source A: the lean dense form only, a.conv == 0)
-             (g_gemm_pp == 1 ||
-              (g_gemm_pp >= 2 && !a.conv && !a.ln_out && !a.b_rows &&
-               ((c.BM == 256 && (c.BN == 256 || (g_gemm_pp == 3 && c.BN == 320))) ||
-                // the long-K two-source 1x1 convs (proj_out o ff.net.2 over (h | g), K = 5C): the ping-pong loop pays
-                // where the K loop is long (unlike the K = 320 / 640 projections, which stay on the two-stage loop)
-                (a.A1 && g_gemm_pp_chain && c.BN == 320 && (c.BM == 256 || c.BM == 128) && a.K >= 1024)))) &&
-             (a.conv || (a.M % c.BM == 0 && a.N % c.BN == 0))) {
-    // ping-pong schedule: 3 stages (BK 32 where BK 64 would not fit); dense GEMMs on whole tiles only (the lean form)
-    const int key = c.BM * 1000 + c.BN;
-    if (key == 256320 || key == 256256 || key == 128320) sp.per *= 2;   // K steps of 32
-    switch (key) {
-      case 256320: launch2<256, 320, 2, 4, 32, 3, 0, true>(b, sp, s); break;
-      case 256256: launch2<256, 256, 2, 4, 32, 3, 0, true>(b, sp, s); break;
-      case 128320: launch2<128, 320, 2, 4, 32, 3, 0, true>(b, sp, s); break;
-      case 256128: launch2<256, 128, 4, 2, 64, 3, 0, true>(b, sp, s); break;
-      case 128256: launch2<128, 256, 2, 4, 64, 3, 0, true>(b, sp, s); break;
-      case 128128: launch2<128, 128, 2, 4, 64, 3, 0, true>(b, sp, s); break;
-      default: return false;
-    }
-  } else if (g_gemm_deep == 2) {   // BK 64; a third (fourth) stage wherever it fits in 160 KiB
-    switch (c.BM * 1000 + c.BN) {
-      case 256256: launch2<256, 256, 2, 4, 64, 2>(b, sp, s); break;
-      case 128320: launch2<128, 320, 2, 4, 64, 2>(b, sp, s); break;
-      case 256128: launch2<256, 128, 4, 2, 64, 3>(b, sp, s); break;
-      case 128256: launch2<128, 256, 2, 4, 64, 3>(b, sp, s); break;
-      case 128128: launch2<128, 128, 2, 4, 64, 4>(b, sp, s); break;
-      case 256160: launch2<256, 160, 4, 2, 64, 3>(b, sp, s); break;
-      default: return false;
-    }
-  } else if (g_gemm_deep == 1) {
-    switch (c.BM * 1000 + c.BN) {
-      case 256256: launch2<256, 256, 2, 4, 32, 4>(b, sp, s); break;
-      case 128320: launch2<128, 320, 2, 4, 32, 5>(b, sp, s); break;
-      case 256128: launch2<256, 128, 4, 2, 32, 5>(b, sp, s); break;
-      case 128256: launch2<128, 256, 2, 4, 32, 5>(b, sp, s); break;
-      case 128128: launch2<128, 128, 2, 4, 32, 6>(b, sp, s); break;
-      default: return false;
-    }
-  } else {
-    switch (c.BM * 1000 + c.BN) {
-      case 256320: launch2<256, 320, 2, 4, 64, 2>(b, sp, s); break;
-      case 256256: launch2<256, 256, 2, 4, 64, 2>(b, sp, s); break;
-      case 128320: launch2<128, 320, 2, 4, 64, 2>(b, sp, s); break;
-      case 256128: launch2<256, 128, 4, 2, 64, 2>(b, sp, s); break;
-      case 128256: launch2<128, 256, 2, 4, 64, 2>(b, sp, s); break;
-      case 128128: launch2<128, 128, 2, 4, 64, 2>(b, sp, s); break;
-      default: return false;
-    }
+#endif
+#define IRX_K2(...) case gemm2_key(__VA_ARGS__): launch2<__VA_ARGS__>(b, sp, s); break;
+  switch (gemm2_key(p.BM, p.BN, p.WM, p.WN, p.BK, p.S, p.HALO, p.PP)) {
+    // halo convs: four 8x8 images per tile (9: parity convs), parity convs on strips / rows, strips, ping-pong, lock-step
+    IRX_K2(256, 160, 4, 2, 64, 3, 9, false)
+    IRX_K2(256, 160, 4, 2, 64, 3, 8, false)
+    IRX_K2(256, 128, 4, 2, 64, 3, 7, false)
+    IRX_K2(256, 160, 4, 2, 64, 3, 6, false)
+    IRX_K2(256, 128, 4, 2, 64, 3, 6, false)
+    IRX_K2(256, 160, 4, 2, 64, 3, 5, false)
+    IRX_K2(256, 128, 4, 2, 64, 3, 5, false)
+    IRX_K2(256, 160, 4, 2, 64, 3, 2, false)
+    IRX_K2(256, 128, 4, 2, 64, 3, 2, false)
+    IRX_K2(256, 160, 4, 2, 64, 3, 1, false)
+    // 64x320 (option gemm_force), the 4-wave 128-row tiles (option gemm_small)
+    IRX_K2(64, 320, 1, 4, 32, 2, 0, false)
+    IRX_K2(128, 160, 2, 2, 64, 2, 0, false)
+    IRX_K2(128, 128, 2, 2, 64, 2, 0, false)
+    // ping-pong main loops
+    IRX_K2(256, 320, 2, 4, 32, 3, 0, true)
+    IRX_K2(256, 256, 2, 4, 32, 3, 0, true)
+    IRX_K2(128, 320, 2, 4, 32, 3, 0, true)
+    IRX_K2(256, 128, 4, 2, 64, 3, 0, true)
+    IRX_K2(128, 256, 2, 4, 64, 3, 0, true)
+    IRX_K2(128, 128, 2, 4, 64, 3, 0, true)
+    // option gemm_deep 2: BK-64 rings (256x256 / 128x320: two stages, shared with the default loop)
+    IRX_K2(256, 256, 2, 4, 64, 2, 0, false)
+    IRX_K2(128, 320, 2, 4, 64, 2, 0, false)
+    IRX_K2(256, 128, 4, 2, 64, 3, 0, false)
+    IRX_K2(128, 256, 2, 4, 64, 3, 0, false)
+    IRX_K2(128, 128, 2, 4, 64, 4, 0, false)
+    IRX_K2(256, 160, 4, 2, 64, 3, 0, false)
+    // option gemm_deep 1: BK-32 rings
+    IRX_K2(256, 256, 2, 4, 32, 4, 0, false)
+    IRX_K2(128, 320, 2, 4, 32, 5, 0, false)
+    IRX_K2(256, 128, 4, 2, 32, 5, 0, false)
+    IRX_K2(128, 256, 2, 4, 32, 5, 0, false)
+    IRX_K2(128, 128, 2, 4, 32, 6, 0, false)
+    // the two-stage BK-64 loop
+    IRX_K2(256, 320, 2, 4, 64, 2, 0, false)
+    IRX_K2(256, 128, 4, 2, 64, 2, 0, false)
+    IRX_K2(128, 256, 2, 4, 64, 2, 0, false)
+    IRX_K2(128, 128, 2, 4, 64, 2, 0, false)
+    default: IRX_CHECK(false, "gemm_large_tile: the plan names a kernel that is not instantiated");
   }
-  return true;
+#undef IRX_K2
 }
 
 }  // namespace irx

@@ -22,7 +22,7 @@
 // tile placement, so the engines stay batch invariant.
 #include <algorithm>
 
-#include "ops.h"
+#include "gemm_plan.h"
 #include "profile.h"
 
 // timing diagnostics only (a separately built library, scripts/build_skdbg.sh): 1 no epilogue / stores, 2 no MFMAs,
@@ -33,12 +33,6 @@
 
 namespace irx {
 
-// irx_set_option("gemm_sk", m): 1 (default) the GEGLU projection only, 3 every K = 320 shape, 2 GEGLU on the one-wave-
-// per-SIMD form, 0 none.  Measured (profiles/r03_kprof_sk_n.txt, M = 65536): GEGLU 179 vs 214 us on the large-tile
-// kernel; the N = 320 / 960 projections 32 / 37 / 74 vs 27 / 34 / 66 us — one wave per SIMD with the B slice in
-// registers leaves the MFMA pipe 14 % busy behind AGPR -> VGPR operand copies and the epilogue's VALU work
-// (profiles/r03_pmc_sk_*.txt), so those stay on the large-tile kernel
-int g_gemm_sk = 1;
 int g_gemm_sk_blocks = 0;   // irx_set_option("gemm_sk_blocks", n): persistent blocks per XCD (0: 32 x blocks per CU)
 
 namespace {
@@ -81,7 +75,7 @@ template <> struct Pk<f16_t> {
   }
 };
 
-constexpr int kSkK = 320;          // the one K this kernel takes
+// (kSkK = 320, gemm_plan.h: the one K this kernel takes)
 constexpr int kSkKS = kSkK / 32;   // 32-deep MFMA K steps
 constexpr int kSkRC = kSkK / 8;    // 16-byte chunks per A row
 
@@ -391,25 +385,6 @@ void launch_sk(const GemmArgs& a, hipStream_t s) {
 }
 
 }  // namespace
-
-// The K = 320 streaming path: dense, 16-bit, one batch, no conv / split / activation / row add / GroupNorm
-// partials; N a multiple of the 320-column slice (GEGLU: of 256 interleaved weight rows); 16-byte aligned rows.
-// The decision depends only on the per-call shape (not on M), so it is the same for every batch size.
-bool gemm_sk_eligible(const GemmArgs& a) {
-  if (!g_gemm_sk || (!a.geglu && g_gemm_sk != 3) || !is16(a.dtype) || a.conv || a.out_f32 || a.batch != 1 || a.K != kSkK) return false;
-  if (a.act != ACT_NONE || a.rowadd || a.gn_part || a.gn_ab || a.b_rows || a.ln_out) return false;
-  if (a.A1 || a.up2_w) return false;   // (one A source of K columns; plain row-major output)
-  if (a.res_rows) return false;        // (the residual DMA walks consecutive rows: no wrap, GemmArgs::res_rows)
-  if (a.geglu ? (a.N % 256 != 0 || a.N / 2 / 128 > 32 || a.residual || a.hs_L || a.ldc % 4) : (a.N % 320 || a.N / 320 > 32))
-    return false;
-  if (a.lda % 8 || a.ldb % 8 || ((uintptr_t)a.A % 16) || ((uintptr_t)a.B % 16)) return false;
-  if (((uintptr_t)a.C % 8) || (a.hs_L ? (a.hs_d % 4 || a.hs_C % 4) : a.ldc % 4)) return false;
-  if (a.residual && (a.ldr % 4 || ((uintptr_t)a.residual % 8))) return false;
-  if (a.hs_L && (a.residual || a.hs_L % 64)) return false;   // (a 64-row tile lies in one image)
-  if ((a.ln_rs || a.ln_part) && (a.alpha != 1.f || a.M % 2)) return false;   // (statistics DMA'd as row pairs)
-  if (a.ln_part && a.ln_T != 1) return false;   // (one producer partial per row: the K = 320 row)
-  return a.M > 0;
-}
 
 bool gemm_sk(const GemmArgs& a0, hipStream_t s) {
   if (!gemm_sk_eligible(a0)) return false;

@@ -791,7 +791,7 @@ size_t Unet::time_table_ws(int n) {
 
 void Unet::time_table(hipStream_t s, const float* t, int n, float* table, char* ws, size_t cap) {
   IRX_CHECK(blob_, "weights not bound");
-  // (rows equal to the per-evaluation chain's while the small-M path takes the GEMMs: gemm.hip small_splits)
+  // (rows equal to the per-evaluation chain's while the small-M path takes the GEMMs: gemm_plan.cpp small_splits)
   IRX_CHECK(n > 0 && n <= 256, "time table: 1 .. 256 timesteps per call");
   Arena ar;
   ar.reset(ws, cap);
@@ -929,8 +929,8 @@ Act Vae::resnet(Ctx& c, const ResW& r, Act& x) {
 // not depend on the blocking.  The key axis is padded to a multiple of 8 (zero probabilities / zero V^T
 // columns) so the PV contraction stays 16-byte aligned.
 constexpr size_t kVaeScoreBytes = 128u << 20;
-int g_vae_attn_rows = 0;
-int g_vae_flash = 1;       // irx_set_option("vae_flash", 0): the row-blocked GEMM form in the 16-bit engines too   // irx_set_option("vae_attn_rows", R): force R query rows per block (tests); 0 = auto
+int g_vae_attn_rows = 0;   // irx_set_option("vae_attn_rows", R): force R query rows per block (tests); 0 = auto
+int g_vae_flash = 1;       // irx_set_option("vae_flash", 0): the row-blocked GEMM form in the 16-bit engines too
 
 Act Vae::attn(Ctx& c, const AttW& a, Act& x) {
   const int B = x.n, HW = x.h * x.w, C = a.c;

@@ -145,66 +145,69 @@ __host__ __device__ __forceinline__ long c_off_f(long m, int n, long ldc, int M,
   return (long)part * M * hs_C + ((img * (hs_C / hs_d) + hd) * hs_L + tok) * hs_d + e;
 }
 #define c_off(a, m, n) c_off_f((m), (n), (a).ldc, (a).M, (a).hs_L, (a).hs_C, (a).hs_d, (a).up2_w, (a).up2_p)
-bool gemm_up2_ok(const GemmArgs& a);   // the large-tile path can store a sub-pixel (GemmArgs::up2_*) output
-void gemm(const GemmArgs& a, hipStream_t s);
-bool gemm_large_tile(const GemmArgs& a, hipStream_t s);   // 8-wave LDS-DMA path; false if not eligible
+void gemm(const GemmArgs& a, hipStream_t s);   // plans the call (gemm_plan.h) and launches the planned kernel
+bool gemm_sk(const GemmArgs& a, hipStream_t s);           // K = 320 streaming path (gemm_sk.hip); false if not eligible
+bool gemm_sk_eligible(const GemmArgs& a);
 float* splitk_scratch(size_t bytes);                     // the library's split-K partial scratch (grown on demand)
-void splitk_reduce(const GemmArgs& a, const float* ws, int splits, int Mp, int Np, hipStream_t s);
-extern int g_small_splitk;   // 1 (default): small-M, long-K 4-wave GEMMs in K splits + the reduce kernel
+// split-K partials ws [batch * splits][Mp][Np] -> C through the full epilogue (gemm2.hip)
+void splitk_reduce(const GemmArgs& a, const float* ws, int splits, int Mp, int Np, int batch, hipStream_t s);
 // A 1x1 / stride-1 / unpadded conv (optionally over a channel concat) rewritten as a dense GEMM over the NHWC
 // rows (A = src0, A1 = src1 from K = C0) when the large-tile path takes it (option conv1x1_dense): the
 // im2col walk's per-tap machinery buys nothing at one tap.  Returns whether `a` was rewritten.
 bool conv1x1_as_dense(GemmArgs& a);
-extern int g_conv1x1_dense;
-bool gemm_sk(const GemmArgs& a, hipStream_t s);           // K = 320 streaming path (gemm_sk.hip); false if not eligible
-bool gemm_sk_eligible(const GemmArgs& a);
-extern int g_gemm_sk;      // 1: the K = 320 projections take gemm_sk (0: the large-tile kernel, A/B)
-extern int g_gemm_sk_blocks;
+// Queries (gemm_plan.cpp): each plans the call with the feature requested and reads the plan gemm() launches from.
 // split-K partial buffer the call will use (an upper bound: the large-tile splits or the 4-wave kernel's small-M
 // splits, whichever path ends up taking the call)
 size_t gemm_workspace_bytes(const GemmArgs& a);
-size_t gemm_small_split_bytes(const GemmArgs& a);         // ... the small-M part (gemm.hip; 0: no such splits)
+size_t gemm_small_split_bytes(const GemmArgs& a);         // ... the small-M part (0: no such splits)
+int gemm_large_splits(const GemmArgs& a);                 // K splits of the large-tile path (0: not on it)
+bool gemm_up2_ok(const GemmArgs& a);          // the large-tile path can store a sub-pixel (GemmArgs::up2_*) output
 bool gemm_geglu_fusable(const GemmArgs& a);               // large-tile path can apply the GEGLU epilogue
 bool gemm_gn_fusable(const GemmArgs& a);                  // conv can apply GemmArgs::gn_ab to its operand
 bool gemm_ln_foldable(const GemmArgs& a);                 // large-tile epilogue can apply GemmArgs::ln_rs / ln_u
 bool gemm_emits_ln_parts(const GemmArgs& a);              // large-tile epilogue can emit GemmArgs::ln_out
-extern int g_up2;            // 1: nearest-2x upsampler convs as 4 per-parity 2x2 convs (IRX_LAYOUT_CONV_UP2; 0: A/B)
-extern int g_ff_chain;       // 1: 16-bit UNets run ff.net.2 -> proj_out as one GEMM (IRX_LAYOUT_MAT_CHAIN; 0: two, A/B)
-extern int g_gn_red_parts;   // 1: split-K reduce kernels emit GroupNorm partials (per 64-row block)
-int gemm_large_splits(const GemmArgs& a);                 // K splits of the large-tile path (0: not on it)
 bool gemm_bimg_ok(const GemmArgs& a);                     // large-tile path can take per-image B / bias (b_rows)
-extern int g_gn_fold;      // 1: the transformer GroupNorm folded into per-image proj_in weights (0: gn_apply, A/B)
-extern int g_ln_parts;     // 1: transformer producers emit LayerNorm partials, the statistics pass is skipped (0: A/B)
-extern int g_ln_fold;      // 1: 16-bit UNets fold LayerNorm into the following projections (read at model creation)
 int gemm_emits_gn_parts(const GemmArgs& a);   // rows per GroupNorm partial this call's epilogue emits (0: none)
-extern int g_gn_parts;     // 1: producers emit GroupNorm partial sums, the stats pass is skipped (0: A/B)
-extern int g_gn_fuse;      // 1: GroupNorm(+SiLU) folded into the following halo conv where it fits (0: A/B)
+// options of the GEMM policy (gemm_plan.cpp says what each does)
 extern bool g_large_tiles;
 extern int g_large_mask;
 extern int g_large_dense;
-extern int g_gemm_pp_chain;   // 1 (default): the long-K two-source 1x1 chains on the lean dense ping-pong loop
-extern int g_gemm_group;   // 1 (default): grouped dense tile order where it cuts per-XCD A + B bytes by > 10 %
-extern int g_halo_mi;      // 1 (default): the 8x8-level 3x3 convs on 4-image halo tiles (K splits, reduce kernel)
-extern int g_halo_up2;     // 1 (default): upsampler parity convs (2x2, GemmArgs::up2_*) on 4-tap halo tiles
-extern int g_halo_strip;   // 1 (default): 8 x 32 strip halo tiles where whole-row tiles do not fit; 2 wherever allowed
-extern int g_halo_group;   // 1 (default): grouped halo conv tile order where it cuts per-XCD A + B bytes by > 10 %
-extern int g_gemm_nmajor;   // 0 M-major tile order, 1 N-major where B outweighs A (default), 2 always N-major
+extern int g_small_splitk;   // 1 (default): small-M, long-K 4-wave GEMMs in K splits + the reduce kernel
+extern int g_gemm_sk;      // 1: the K = 320 projections take gemm_sk (0: the large-tile kernel, A/B)
 extern int g_gemm_deep;    // large-tile pipeline: 0 two-stage BK 64, 1 BK-32 S-stage ring, 2 BK-64 deeper ring
-extern int g_gemm_dbg;     // timing diagnostics only: results are wrong when set
 extern bool g_gemm_small;  // short-K GEMMs on 4-wave 128x160 / 128x128 tiles, 2 blocks per CU
 extern int g_gemm_small_kmax;
+extern int g_gemm_force;
+extern bool g_tile_256x320;
+extern bool g_splitk_inkernel;
+extern int g_gemm_nmajor;   // 0 M-major tile order, 1 N-major where B outweighs A (default), 2 always N-major
+extern int g_gemm_group;   // 1 (default): grouped dense tile order where it cuts per-XCD A + B bytes by > 10 %
+extern int g_gemm_pp;        // 1: ping-pong main loop for dense GEMMs (off: measured slower, see gemm_plan.cpp)
+extern int g_gemm_pp_chain;   // 1 (default): the long-K two-source 1x1 chains on the lean dense ping-pong loop
+extern int g_conv1x1_dense;
+extern int g_conv_halo;      // 3x3 convs on whole-row tiles: one LDS halo per 32-channel slab for all 9 taps
+extern int g_halo_split;     // halo convs whose tiles alone do not fill the chip take two K splits
+extern int g_halo_pipe;      // 1: software-pipelined halo main loop (fragments read one sub-step ahead)
+extern int g_halo_strip;   // 1 (default): 8 x 32 strip halo tiles where whole-row tiles do not fit; 2 wherever allowed
+extern int g_halo_up2;     // 1 (default): upsampler parity convs (2x2, GemmArgs::up2_*) on 4-tap halo tiles
+extern int g_halo_mi;      // 1 (default): the 8x8-level 3x3 convs on 4-image halo tiles (K splits, reduce kernel)
+extern int g_halo_group;   // 1 (default): grouped halo conv tile order where it cuts per-XCD A + B bytes by > 10 %
+extern int g_gn_fuse;      // 1: GroupNorm(+SiLU) folded into the following halo conv where it fits (0: A/B)
+extern int g_gn_parts;     // 1: producers emit GroupNorm partial sums, the stats pass is skipped (0: A/B)
+extern int g_gn_red_parts;   // 1: split-K reduce kernels emit GroupNorm partials (per 64-row block)
+extern int g_gn_fold;      // 1: the transformer GroupNorm folded into per-image proj_in weights (0: gn_apply, A/B)
+extern int g_ln_fold;      // 1: 16-bit UNets fold LayerNorm into the following projections (read at model creation)
+extern int g_ln_parts;     // 1: transformer producers emit LayerNorm partials, the statistics pass is skipped (0: A/B)
+// launch-side options (gemm_sk.hip, gemm2.hip) and the models' GEMM-shaped choices (models.cpp)
+extern int g_gemm_sk_blocks;
+extern int g_gemm_dbg;     // timing diagnostics only: results are wrong when set
+extern int g_up2;            // 1: nearest-2x upsampler convs as 4 per-parity 2x2 convs (IRX_LAYOUT_CONV_UP2; 0: A/B)
+extern int g_ff_chain;       // 1: 16-bit UNets run ff.net.2 -> proj_out as one GEMM (IRX_LAYOUT_MAT_CHAIN; 0: two, A/B)
 
 // ------------------------------------------------------------ normalisation
 // GroupNorm over NHWC (optionally a channel concat of two sources). Writes the normalised (and
 // optionally SiLU'd) result as one contiguous C0+C1 channel tensor.  `ws` needs gn_ws_bytes().
 size_t gn_ws_bytes(int N, int HW, int G);
-extern bool g_splitk_inkernel;
-extern bool g_tile_256x320;
-extern int g_gemm_force;
-extern int g_conv_halo;      // 3x3 convs on whole-row tiles: one LDS halo per 32-channel slab for all 9 taps
-extern int g_gemm_pp;        // 1: ping-pong main loop for dense GEMMs (off: measured slower, see gemm2.hip)
-extern int g_halo_pipe;      // 1: software-pipelined halo main loop (fragments read one sub-step ahead)
-extern int g_halo_split;     // halo convs whose tiles alone do not fill the chip take two K splits
 extern int g_gn_fa;        // GroupNorm from partials as one fused finalize + apply launch (gn_fa_kernel) at HW <= g_gn_fa
 extern int g_gn_fa_wide;
 extern int g_gn_fa_blocks;

@@ -2,7 +2,7 @@
 """Tile / split-K sweep over the conv and GEMM shapes of one batch-16 UNet eval and a batch-8 VAE pass.
 For every shape: time the heuristic's choice (gemm_force 0) and every forced (BM, BN, splits) candidate
 (HIP events, interleaved repeats); print the best and the heuristic's loss.  Calibration data for
-gemm2.hip choose().  Usage: python scripts/gemm_sweep.py [--iters 10] [--only unet|vae]"""
+gemm_plan.cpp choose().  Usage: python scripts/gemm_sweep.py [--iters 10] [--only unet|vae]"""
 import argparse
 import math
 import sys

@@ -1,4 +1,4 @@
-"""K-split partials of the small-M GEMMs (the time embedding's linear_2, gemm.hip small_splits) live in the caller's
+"""K-split partials of the small-M GEMMs (the time embedding's linear_2, gemm_plan.cpp small_splits) live in the caller's
 workspace: gemm_workspace_bytes reports them and the models carve them from their arena, so a captured denoising loop
 holds no pointer into the library's grow-on-demand scratch, which a later call with more rows frees and reallocates."""
 import numpy as np
