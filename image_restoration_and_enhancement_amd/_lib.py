@@ -112,6 +112,9 @@ _SIGS = {
     "irx_degrade_blur_down": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]),
     "irx_degrade_gray": (i32, [vp, vp, i64, i32, i32, vp]),
     "irx_degrade_strokes": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "irx_degrade_motion_blur": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "irx_degrade_jpeg_ws_bytes": (i64, [i32, i32, i32]),
+    "irx_degrade_jpeg": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp]),
     "irx_nlm_weights": (i32, [f32, i32, i32, i32, C.POINTER(i32), i32, C.POINTER(i32)]),
     "irx_nlmeans_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32]),
     "irx_bilateral_tables": (i32, [i32, C.c_double, C.c_double, i32, vp, vp, vp, i32, C.POINTER(i32),

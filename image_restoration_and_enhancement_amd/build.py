@@ -28,7 +28,8 @@ BASE_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "
 PER_FILE = {"elementwise.hip": ["-ffp-contract=off"],
             "attention.hip": ["-fno-honor-nans"],
             "filters.hip": ["-ffp-contract=off"],
-            "degrade.hip": ["-ffp-contract=off"]}
+            "degrade.hip": ["-ffp-contract=off"],
+            "degrade_jpeg.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

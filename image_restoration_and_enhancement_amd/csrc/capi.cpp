@@ -477,6 +477,26 @@ int irx_degrade_strokes(void* s, int batch, int H, int W, const int* segs, const
   if (batch) degrade_strokes(batch, H, W, segs, thick, seg_off, mask, img, masked, S(s));
   IRX_API_END
 }
+int irx_degrade_motion_blur(void* s, const uint8_t* img, int batch, int H, int W, int C, const int* taps,
+                            const int* tap_off, uint8_t* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(img && taps && tap_off && out && batch >= 0 && (C == 1 || C == 3), "bad arguments");
+  IRX_CHECK(H >= 8 && W >= 8, "motion blur: H, W >= 8");
+  if (batch) degrade_motion_blur(img, batch, H, W, C, taps, tap_off, out, S(s));
+  IRX_API_END
+}
+long irx_degrade_jpeg_ws_bytes(int batch, int H, int W) {
+  if (batch < 0 || H < 8 || W < 8) return 0;
+  return degrade_jpeg_ws_bytes(batch, H, W);
+}
+int irx_degrade_jpeg(void* s, const uint8_t* img, int batch, int H, int W, const int* qtables, int rgb, void* ws,
+                     uint8_t* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(H >= 8 && W >= 8, "JPEG round trip: H, W >= 8");
+  IRX_CHECK(img && qtables && out && batch >= 0 && (ws || batch == 0), "bad arguments");
+  if (batch) degrade_jpeg(img, batch, H, W, qtables, rgb, ws, out, S(s));
+  IRX_API_END
+}
 
 // ------------------------------------------------------------------ fast non-local means
 static int nlm_shift(int tmpl) {

@@ -11,6 +11,9 @@
 //     "lab" = L of BGR2Lab (sRGB linearisation, CIE L*, * 255 / 100), restated in fp32;
 //   * random_free_form_mask (:104-114): thick cv2.line strokes rasterised as capsules (distance to the
 //     segment <= thickness / 2, exact int64 test), and the masked input img * (mask == 0) (:196-198).
+//   * add_motion_blur     (:46-64): cv2.filter2D with the line kernel given as a per-image tap list; fp32
+//     accumulation in raster tap order, BORDER_REFLECT_101, rint.
+// The JPEG round trip (:38-43) lives in degrade_jpeg.hip.
 // All kernels are HBM-bound byte work: one pass, 16-byte-coalesced where the layout allows, no LDS.
 #include "ops.h"
 #include "profile.h"
@@ -225,6 +228,46 @@ __global__ __launch_bounds__(256) void stroke_kernel(int B, int H, int W, const 
   }
 }
 
+// taps: [ntap][2] (dy, dx) offsets from the anchor, tap_off: [B+1] (image b owns taps tap_off[b] ..
+// tap_off[b+1], in raster order).  cv2.filter2D's arithmetic for a kernel whose non-zero cells all equal
+// 1 / n: an fp32 accumulator per sample, one rounding per product and per sum, then rint and saturation.
+// A lane owns 4 consecutive bytes of one image row (W * C bytes); a tap shifts the row by dx * C bytes, so away
+// from the left and right borders its 4 sources are one (unaligned) dword.  blockIdx.y is the image: the tap
+// list is wave-uniform.
+__global__ __launch_bounds__(256) void motion_blur_kernel(const uint8_t* __restrict__ img, int H, int W, int C,
+                                                          const int* __restrict__ taps,
+                                                          const int* __restrict__ tap_off,
+                                                          uint8_t* __restrict__ out) {
+  const int b = blockIdx.y, RW = W * C, chunks = (RW + 3) / 4;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)H * chunks) return;
+  const int y = (int)(i / chunks), j0 = (int)(i % chunks) * 4;
+  const int t0 = tap_off[b], t1 = tap_off[b + 1];
+  const uint8_t* base = img + (long)b * H * RW;
+  const float coef = __fdiv_rn(1.f, (float)max(t1 - t0, 1));
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int t = t0; t < t1; ++t) {
+    const uint8_t* row = base + (long)reflect101(y + taps[2 * t], H) * RW;
+    const int dx = taps[2 * t + 1], js = j0 + dx * C;
+    uint8_t v[4];
+    if (js >= 0 && js + 3 < RW && j0 + 3 < RW) {
+      __builtin_memcpy(v, row + js, 4);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int j = min(j0 + e, RW - 1), x = j / C;
+        v[e] = row[reflect101(x + dx, W) * C + (j - x * C)];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = __fadd_rn(acc[e], __fmul_rn(coef, (float)v[e]));
+  }
+  uint8_t* o = out + ((long)b * H + y) * RW + j0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (j0 + e < RW) o[e] = (uint8_t)fminf(fmaxf(rintf(acc[e]), 0.f), 255.f);
+}
+
 unsigned blocks(long n, int per_thread = 1) { return (unsigned)((n / per_thread + 255) / 256 + 1); }
 
 }  // namespace
@@ -258,6 +301,15 @@ void degrade_strokes(int B, int H, int W, const int* segs, const int* thick, con
                      const uint8_t* img, uint8_t* masked, hipStream_t s) {
   stroke_kernel<<<dim3((W + kStrokeT - 1) / kStrokeT, (H + kStrokeT - 1) / kStrokeT, B), 256, 0, s>>>(
       B, H, W, segs, thick, seg_off, mask, img, masked);
+  IRX_LAUNCH_CHECK();
+}
+
+void degrade_motion_blur(const uint8_t* img, int B, int H, int W, int C, const int* taps, const int* tap_off,
+                         uint8_t* out, hipStream_t s) {
+  const long per = (long)H * (((long)W * C + 3) / 4);          // a lane per 4 bytes of a row
+  IRX_CHECK(B <= 65535 && (long)W * C < (1L << 30) && (per + 255) / 256 < (1L << 31),
+            "batch or image too large for one launch");
+  motion_blur_kernel<<<dim3((unsigned)((per + 255) / 256), B), 256, 0, s>>>(img, H, W, C, taps, tap_off, out);
   IRX_LAUNCH_CHECK();
 }
 

@@ -337,6 +337,12 @@ void degrade_blur_down(const uint8_t* img, int B, int H, int W, int C, const int
 void degrade_gray(const uint8_t* img, long npix, int mode, int rgb, uint8_t* out, hipStream_t s);
 void degrade_strokes(int B, int H, int W, const int* segs, const int* thick, const int* seg_off, uint8_t* mask,
                      const uint8_t* img, uint8_t* masked, hipStream_t s);
+void degrade_motion_blur(const uint8_t* img, int B, int H, int W, int C, const int* taps, const int* tap_off,
+                         uint8_t* out, hipStream_t s);
+// JPEG round trip (degrade_jpeg.hip): qt_dev int[B][2][64]; ws of degrade_jpeg_ws_bytes, 8-byte aligned
+long degrade_jpeg_ws_bytes(int B, int H, int W);
+void degrade_jpeg(const uint8_t* img, int B, int H, int W, const int* qt_dev, int rgb, void* ws, uint8_t* out,
+                  hipStream_t s);
 
 
 // ------------------------------------------------------------ fast non-local means (nlmeans.hip)

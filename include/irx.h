@@ -221,6 +221,20 @@ int irx_degrade_gray(void* stream, const uint8_t* img, long npix, int mode, int 
  * seg_off int[batch+1]; mask [batch][H][W] = 255 inside any stroke; img/masked (nullable) [batch][H][W][3] */
 int irx_degrade_strokes(void* stream, int batch, int H, int W, const int* segs, const int* thick, const int* seg_off,
                         uint8_t* mask, const uint8_t* img, uint8_t* masked);
+/* add_motion_blur (:46-64): cv2.filter2D(img, -1, kernel) for the line kernel whose non-zero cells (all 1/n) are
+ * image b's taps[tap_off[b] .. tap_off[b+1]) (int[ntap][2] = (dy, dx) from the centre, raster order; tap_off
+ * int[batch+1]; both device memory).  BORDER_REFLECT_101, fp32 accumulation in tap order, rint.  img/out
+ * [batch][H][W][C], C = 1 or 3; H, W >= 8 */
+int irx_degrade_motion_blur(void* stream, const uint8_t* img, int batch, int H, int W, int C, const int* taps,
+                            const int* tap_off, uint8_t* out);
+/* add_jpeg_compression (:38-43): the decoded pixels of cv2.imencode('.jpg') -> cv2.imdecode for a baseline 4:2:0
+ * JPEG with image b's quantisation tables qtables[b][2][64] (device int; luma, chroma; natural order, 1..255):
+ * libjpeg's integer chain without the (lossless) entropy coder.  img/out [batch][H][W][3], rgb != 0: channel
+ * order R,G,B; H, W >= 8.  ws: irx_degrade_jpeg_ws_bytes(batch, H, W) bytes of device memory, 8-byte aligned
+ * (0 is returned for arguments irx_degrade_jpeg would refuse) */
+long irx_degrade_jpeg_ws_bytes(int batch, int H, int W);
+int irx_degrade_jpeg(void* stream, const uint8_t* img, int batch, int H, int W, const int* qtables, int rgb,
+                     void* ws, uint8_t* out);
 
 /* ---- fast non-local means (cv2.fastNlMeansDenoising / ...Colored as src/inference.py:509-515 calls them in the
  * classical denoise fallback _denoise_opencv :500-522).  OpenCV's integer invoker, exact. ---- */

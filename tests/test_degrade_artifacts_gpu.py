@@ -1,0 +1,186 @@
+"""GPU parity of the JPEG round-trip and motion-blur kernels (csrc/degrade_jpeg.hip, csrc/degrade.hip) and of the
+generator modes built on them, bit for bit: JPEG against Pillow + libjpeg-turbo and the integer restatement
+`degrade_host.jpeg_roundtrip_ref`; motion blur against the fp32 restatement `degrade_host.motion_blur_ref`
+(parity with cv2.filter2D itself is unpinned: OpenCV is absent); degrade_sr / make_pairs against the composition
+of the host references under the replayed draws."""
+import ctypes as C
+import io
+import random
+
+import numpy as np
+import pytest
+import torch
+
+from image_restoration_and_enhancement_amd import _lib as L
+from image_restoration_and_enhancement_amd import degrade as D
+from image_restoration_and_enhancement_amd import degrade_host as DH
+from tests import degrade_replay as P
+
+pytestmark = pytest.mark.gpu
+
+
+def _img(shape, seed=0):
+    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
+
+
+def _mixed(B, H, W, seed):
+    """Noise, a smooth field and their blend: busy and nearly-empty DCT blocks both occur."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    smooth = (128 + 100 * np.sin(yy / 7.0 + xx / 5.0))[..., None] + np.arange(3) * 20
+    out = []
+    for b in range(B):
+        noise = rng.integers(0, 256, (H, W, 3))
+        w = (0.0, 1.0, 0.5)[b % 3]
+        out.append(np.clip(w * noise + (1 - w) * smooth + rng.normal(0, 3, (H, W, 3)), 0, 255).astype(np.uint8))
+    return np.stack(out)
+
+
+def _pillow_roundtrip(rgb, q):
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(rgb).save(buf, "JPEG", quality=q)
+    buf.seek(0)
+    return np.asarray(Image.open(buf).convert("RGB"))
+
+
+def _seed(s):
+    random.seed(s)
+    np.random.seed(s)
+
+
+@pytest.mark.parametrize("H,W", [(8, 8), (17, 33), (20, 16), (22, 35), (40, 48), (64, 64)])
+def test_jpeg_roundtrip_bit_exact(device, H, W):
+    from PIL import features
+    qs = (30, 75, 95)
+    imgs = _mixed(3, H, W, seed=H * 100 + W)
+    t = torch.from_numpy(imgs).to(device)
+    got_rgb = D.jpeg_roundtrip(t, qs, rgb=True).cpu().numpy()
+    got_bgr = D.jpeg_roundtrip(t.flip(-1), qs).cpu().numpy()
+    for b, q in enumerate(qs):
+        ref = DH.jpeg_roundtrip_ref(imgs[b], q, rgb=True)
+        assert np.array_equal(got_rgb[b], ref), (b, q)
+        assert np.array_equal(got_bgr[b], DH.jpeg_roundtrip_ref(np.ascontiguousarray(imgs[b][..., ::-1]), q))
+        assert np.array_equal(got_bgr[b][..., ::-1], ref)
+        if features.check_feature("libjpeg_turbo"):
+            assert np.array_equal(got_rgb[b], _pillow_roundtrip(imgs[b], q)), (b, q)
+    # a single image takes the same path
+    one = D.jpeg_roundtrip(t[1], [75], rgb=True).cpu().numpy()
+    assert np.array_equal(one, got_rgb[1])
+
+
+def test_jpeg_tile_boundaries_and_extreme_qualities(device):
+    """More than one 4-MCU tile per row with a partial last tile (W = 150), and the table extremes."""
+    imgs = _mixed(3, 24, 150, seed=11)
+    qs = (1, 50, 100)
+    got = D.jpeg_roundtrip(torch.from_numpy(imgs).to(device), qs, rgb=True).cpu().numpy()
+    for b, q in enumerate(qs):
+        assert np.array_equal(got[b], DH.jpeg_roundtrip_ref(imgs[b], q, rgb=True)), q
+
+
+MOTION = [(3, 0.0), (6, 33.3), (12, 135.0), (15, 359.0)]
+
+
+@pytest.mark.parametrize("H,W,Cc", [(8, 8, 3), (9, 23, 3), (37, 50, 3), (64, 64, 3), (37, 50, 1)])
+def test_motion_blur_bit_exact(device, H, W, Cc):
+    taps = [DH.motion_kernel_taps(k, a)[0] for k, a in MOTION]
+    imgs = _img((4, H, W, Cc), seed=H + W + Cc)
+    got = D.motion_blur(torch.from_numpy(imgs).to(device), taps).cpu().numpy()
+    for b in range(4):
+        assert np.array_equal(got[b], DH.motion_blur_ref(imgs[b], taps[b])), MOTION[b]
+    one = D.motion_blur(torch.from_numpy(imgs[2]).to(device), [taps[2]]).cpu().numpy()
+    assert np.array_equal(one, got[2])
+
+
+def test_add_ops_draw_and_match(device):
+    img = _img((24, 40, 3), seed=2)
+    t = torch.from_numpy(img).to(device)
+    _seed(4)
+    j = D.add_jpeg_compression(t).cpu().numpy()
+    m = D.add_motion_blur(t).cpu().numpy()
+    _seed(4)
+    q = random.randint(30, 90)
+    k = random.randint(5, 15)
+    taps = DH.motion_kernel_taps(k, random.uniform(0, 360))[0]
+    assert np.array_equal(j, DH.jpeg_roundtrip_ref(img, q))
+    assert np.array_equal(m, DH.motion_blur_ref(img, taps))
+
+
+# seeds whose first random.random() is below / above 0.3: the motion-blur and the Gaussian branch of degrade_sr
+SR_SEED_MOTION, SR_SEED_GAUSS = 1, 0
+
+
+@pytest.mark.parametrize("use_jpeg,use_motion_blur,seed,motion", [
+    (True, False, SR_SEED_MOTION, False), (False, True, SR_SEED_MOTION, True), (False, True, SR_SEED_GAUSS, False),
+    (True, True, SR_SEED_MOTION, True), (True, True, SR_SEED_GAUSS, False)])
+def test_degrade_sr_with_flags(device, use_jpeg, use_motion_blur, seed, motion):
+    imgs = _img((6, 64, 48, 3), seed=9)
+    _seed(seed)
+    got = D.degrade_sr(torch.from_numpy(imgs).to(device), 4, use_jpeg=use_jpeg, use_motion_blur=use_motion_blur)
+    _seed(seed)
+    p = P.replay_degrade_sr(use_jpeg, use_motion_blur)
+    assert (p["motion"] is not None) == motion                 # the branch this case is here for
+    assert got.shape == (6, 16, 12, 3)
+    for b in range(6):
+        assert np.array_equal(got[b].cpu().numpy(), P.expected_sr(imgs[b], p, 4)), b
+
+
+MAKE_PAIRS_SEED = 2      # the first seed whose six images take every branch (asserted below)
+
+
+def test_make_pairs_all_flags(device):
+    B, H, W = 6, 64, 48
+    imgs = _mixed(B, H, W, seed=5)
+    _seed(MAKE_PAIRS_SEED)
+    out = D.make_pairs(torch.from_numpy(imgs).to(device), grayscale_mode="simple", denoise_with_artifacts=True,
+                       sr_with_jpeg=True, sr_with_motion_blur=True)
+    _seed(MAKE_PAIRS_SEED)
+    per = P.replay_make_pairs(B, H, W, True, True, True)
+    # every branch occurs in this batch: JPEG / no JPEG, blur / no blur, JPEG then blur, both SR blurs, both masks
+    assert {p["dn_q"] is not None for p in per} == {False, True}
+    assert {p["dn_motion"] is not None for p in per} == {False, True}
+    assert any(p["dn_q"] is not None and p["dn_motion"] is not None for p in per)
+    assert {p["sr"]["motion"] is not None for p in per} == {False, True}
+    assert {p["easy"] for p in per} == {False, True}
+    exp = P.expected_pairs(imgs, per, 4)
+    assert set(out) == set(exp)
+    for key, ref in exp.items():
+        assert np.array_equal(out[key].cpu().numpy(), ref), key
+
+
+def test_make_pairs_without_flags_is_unchanged(device):
+    """The flags off: the draws and bytes of the old ops alone (noise, Gaussian + cubic, gray, strokes)."""
+    B, H, W = 3, 64, 48
+    imgs = _img((B, H, W, 3), seed=6)
+    _seed(8)
+    out = D.make_pairs(torch.from_numpy(imgs).to(device), grayscale_mode="simple")
+    after = random.getstate()
+    _seed(8)
+    per = P.replay_make_pairs(B, H, W, False, False, False)
+    assert after == random.getstate()
+    assert all(5 <= p["sigma"] <= 8 and p["sr"]["k"] in (3, 5, 7) for p in per)
+    for key, ref in P.expected_pairs(imgs, per, 4).items():
+        assert np.array_equal(out[key].cpu().numpy(), ref), key
+
+
+def test_c_abi_argument_checks(device):
+    lib = L.load()
+    x = torch.zeros((1, 16, 16, 3), dtype=torch.uint8, device=device)
+    out = torch.empty_like(x)
+    qt = torch.from_numpy(DH.jpeg_quant_tables(50)[None]).to(device)
+    n = L.call("irx_degrade_jpeg_ws_bytes", 1, 16, 16)
+    assert n > 0 and L.call("irx_degrade_jpeg_ws_bytes", 2, 17, 33) == 2 * 32 * 48 * 3 // 2
+    ws = torch.empty(n, dtype=torch.uint8, device=device)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    assert lib.irx_degrade_jpeg(None, p(x), 1, 4, 16, p(qt), 0, p(ws), p(out)) != 0
+    assert b"H, W >= 8" in lib.irx_last_error()
+    assert lib.irx_degrade_jpeg(None, p(x), 1, 16, 16, None, 0, p(ws), p(out)) != 0
+    assert b"bad arguments" in lib.irx_last_error()
+    assert lib.irx_degrade_jpeg(None, p(x), 0, 16, 16, p(qt), 0, None, p(out)) == 0          # batch 0: no-op
+    tp = torch.zeros((1, 2), dtype=torch.int32, device=device)
+    of = torch.tensor([0, 1], dtype=torch.int32, device=device)
+    assert lib.irx_degrade_motion_blur(None, p(x), 1, 16, 4, 3, p(tp), p(of), p(out)) != 0
+    assert b"H, W >= 8" in lib.irx_last_error()
+    assert lib.irx_degrade_motion_blur(None, p(x), 1, 16, 16, 3, None, p(of), p(out)) != 0
+    with pytest.raises(L.IrxError):
+        D.jpeg_roundtrip(torch.zeros((4, 16, 3), dtype=torch.uint8, device=device), [50])
