@@ -125,8 +125,6 @@ static const struct { const char* name; int* i; bool* b; } kOpts[] = {
     {"attn_xcd", &g_attn_xcd, nullptr},
     {"attn_hm", &g_attn_hm, nullptr},
     {"gemm_small_kmax", &g_gemm_small_kmax, nullptr},
-    {"nlm_strip", &g_nlm_strip, nullptr},
-    {"nlm_v2", &g_nlm_v2, nullptr},
     {"nlm2_strip", &g_nlm2_strip, nullptr},
 };
 static OptRef opt_ref(const std::string& n) {

@@ -128,6 +128,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm2_kern
   constexpr int KSUB = BK / 32;              // 32-deep MFMA sub-steps per stage
   static_assert((NW == 8 || NW == 4) && ROWS % RPI == 0 && BM % 16 == 0 && (BK == 32 || BK == 64), "tile shape");
   static_assert(!HALO || (CONV && !RESIZE && S >= 2 && S <= 8 && NW == 8), "halo tiles: 3x3 conv");
+  static_assert(!PP || !CONV, "ping-pong: dense GEMMs only");
   // HALO == 5: the ping-pong halo loop over 8-row x 32-column strip tiles (images wider than kHaloWMax, or rows
   // that are no power of two): the tile's GEMM rows are the strip's pixels in (row, column) order (host: the
   // tiles of an image are its strips, row block major), the halo is 10 rows x 32 columns plus the two
@@ -792,7 +793,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm2_kern
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-  } else if constexpr (PP && !CONV) {
+  } else if constexpr (PP) {
     // ---- lean ping-pong for dense GEMMs (host: whole tiles, M % BM == N % BN == 0): the halo loop's form.  The
     //      waves w and w + 4 sharing a SIMD alternate a load phase (this wave's fragment reads of step kt, then its
     //      LDS-DMA pieces of step kt + 2) and a compute phase (step kt's MFMAs), group 1 one phase behind group 0.
@@ -901,75 +902,6 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm2_kern
       });
     }
     if (!g1) barrier(true);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  } else if constexpr (PP) {
-    // ---- ping-pong main loop (the dense GEMM / im2col conv counterpart of the HALO == 2 schedule): the waves
-    //      w and w + 4 sharing a SIMD alternate between a load phase (LDS-DMA of step kt + 2, this wave's
-    //      fragment reads of step kt) and a compute phase (step kt's MFMAs), group 1 one phase behind group 0,
-    //      so every interval between barriers pairs one wave's MFMAs with its partner's loads.  S = 3 stages:
-    //      step kt + 2 goes into the stage of step kt - 1, whose fragments every wave read before the barrier
-    //      that ended its own load phase of kt - 1 (lgkmcnt(0) in `barrier`).  Each wave issues its IPW pieces
-    //      of every step; group 1 waits for its pieces of step kt + 1 at the end of its load phase of kt,
-    //      group 0 at the end of its compute phase of kt — both right before the barrier after which group 0
-    //      reads step kt + 1.
-    static_assert(S == 3 && NW == 8, "ping-pong: 3 stages, 8 waves");
-    const int wv = __builtin_amdgcn_readfirstlane(wave);
-    const bool g1 = wv >= NW / 2;
-    uint4 fa[KSUB][TM], fb[KSUB][TN];
-    auto readF = [&](int st) {
-      const uint4* As = smem + st * STAGE;
-      const uint4* Bs = As + BM * CPR;
-#pragma unroll
-      for (int s = 0; s < KSUB; ++s) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const int r = wm * TM * 16 + i * 16 + frow;
-          fa[s][i] = As[r * CPR + ((s * 4 + fgrp) ^ swz(r))];
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int r = wn * TN * 16 + j * 16 + frow;
-          fb[s][j] = Bs[r * CPR + ((s * 4 + fgrp) ^ swz(r + BM))];
-        }
-      }
-    };
-    auto mma = [&]() {
-      if (a.dbg & kDbgMask & 2) return;
-#pragma unroll
-      for (int s = 0; s < KSUB; ++s)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = Mfma<T>::m16x16x32(fa[s][i], fb[s][j], acc[i][j]);
-    };
-    auto barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-    if (kt0 < kt1) issue(kt0, 0);
-    if (kt0 + 1 < kt1) issue(kt0 + 1, 1);
-    wait_vm(kt0 + 1 < kt1 ? IPW : 0);
-    barrier();
-    if (g1) barrier();
-    int st = 0;
-    for (int kt = kt0; kt < kt1; ++kt) {
-      const int st2 = st == 0 ? 2 : st - 1;              // the stage of step kt - 1 == that of kt + 2
-      // ---- load phase
-      if (kt + 2 < kt1) issue(kt + 2, st2);
-      readF(st);
-      if (g1 && kt + 1 < kt1) {
-        if (kt + 2 < kt1) wait_vm(IPW);
-        else wait_vm(0);
-      }
-      barrier();
-      // ---- compute phase
-      mma();
-      if (!g1 && kt + 1 < kt1) {
-        if (kt + 2 < kt1) wait_vm(IPW);
-        else wait_vm(0);
-      }
-      barrier();
-      st = st == 2 ? 0 : st + 1;
-    }
-    if (!g1) barrier();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   } else if constexpr (S == 2) {
@@ -1590,8 +1522,12 @@ void launch2_t(const GemmArgs& a, const Split& sp, hipStream_t s) {
     if constexpr (HALO != 0) {
       gemm2_kernel<T, BM, BN, WM, WN, BK, S, true, false, false, HALO><<<grid, block, 0, s>>>(ea, sp);
     } else if (a.conv) {   // (fp32-output convs never take this path: see eligible())
-      if (rs) gemm2_kernel<T, BM, BN, WM, WN, BK, S, true, false, true, 0, PP><<<grid, block, 0, s>>>(ea, sp);
-      else gemm2_kernel<T, BM, BN, WM, WN, BK, S, true, false, false, 0, PP><<<grid, block, 0, s>>>(ea, sp);
+      if constexpr (PP) {   // (the planner never pairs the ping-pong loop with a conv: large_kernel())
+        IRX_CHECK(false, "gemm_large_tile: the ping-pong loop takes dense GEMMs only");
+      } else {
+        if (rs) gemm2_kernel<T, BM, BN, WM, WN, BK, S, true, false, true><<<grid, block, 0, s>>>(ea, sp);
+        else gemm2_kernel<T, BM, BN, WM, WN, BK, S, true, false, false><<<grid, block, 0, s>>>(ea, sp);
+      }
     } else {
       if (a.out_f32) gemm2_kernel<T, BM, BN, WM, WN, BK, S, false, true, false, 0, PP><<<grid, block, 0, s>>>(ea, sp);
       else gemm2_kernel<T, BM, BN, WM, WN, BK, S, false, false, false, 0, PP><<<grid, block, 0, s>>>(ea, sp);
@@ -1714,16 +1650,11 @@ void gemm_large_tile(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
     IRX_K2(64, 320, 1, 4, 32, 2, 0, false)
     IRX_K2(128, 160, 2, 2, 64, 2, 0, false)
     IRX_K2(128, 128, 2, 2, 64, 2, 0, false)
-    // ping-pong main loops
+    // the lean ping-pong loop (dense GEMMs on whole tiles): 256x256, and the long-K two-source chains' 320-column tiles
     IRX_K2(256, 320, 2, 4, 32, 3, 0, true)
     IRX_K2(256, 256, 2, 4, 32, 3, 0, true)
     IRX_K2(128, 320, 2, 4, 32, 3, 0, true)
-    IRX_K2(256, 128, 4, 2, 64, 3, 0, true)
-    IRX_K2(128, 256, 2, 4, 64, 3, 0, true)
-    IRX_K2(128, 128, 2, 4, 64, 3, 0, true)
-    // option gemm_deep 2: BK-64 rings (256x256 / 128x320: two stages, shared with the default loop)
-    IRX_K2(256, 256, 2, 4, 64, 2, 0, false)
-    IRX_K2(128, 320, 2, 4, 64, 2, 0, false)
+    // option gemm_deep 2: BK-64 rings of three / four stages (256x256 / 128x320 fit two: the two-stage loop below)
     IRX_K2(256, 128, 4, 2, 64, 3, 0, false)
     IRX_K2(128, 256, 2, 4, 64, 3, 0, false)
     IRX_K2(128, 128, 2, 4, 64, 4, 0, false)
@@ -1734,8 +1665,10 @@ void gemm_large_tile(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
     IRX_K2(256, 128, 4, 2, 32, 5, 0, false)
     IRX_K2(128, 256, 2, 4, 32, 5, 0, false)
     IRX_K2(128, 128, 2, 4, 32, 6, 0, false)
-    // the two-stage BK-64 loop
+    // the two-stage BK-64 loop (dense GEMMs and im2col convs)
     IRX_K2(256, 320, 2, 4, 64, 2, 0, false)
+    IRX_K2(256, 256, 2, 4, 64, 2, 0, false)
+    IRX_K2(128, 320, 2, 4, 64, 2, 0, false)
     IRX_K2(256, 128, 4, 2, 64, 2, 0, false)
     IRX_K2(128, 256, 2, 4, 64, 2, 0, false)
     IRX_K2(128, 128, 2, 4, 64, 2, 0, false)

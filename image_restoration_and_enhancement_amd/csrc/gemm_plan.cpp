@@ -27,11 +27,9 @@ bool g_tile_256x320 = true;      // irx_set_option("tile_256x320", 0): no 256x32
 bool g_splitk_inkernel = true;   // irx_set_option("splitk_inkernel", 0): separate split-K reduce kernel (A/B)
 int g_gemm_nmajor = 1;   // 0 M-major tile order, 1 N-major where B outweighs A (default), 2 always N-major
 int g_gemm_group = 1;    // irx_set_option("gemm_group", 0): the M-major / N-major dense tile orders only (A/B)
-// irx_set_option("gemm_pp", m): ping-pong main loops.  2 (default): the lean dense form on 256x256 tiles only (the
-// 32x32 / 16x16-level GEGLU projections: ff1 -12 / -14 % at the kbench shapes, 49.9 -> 46.5 ms/step in the bench;
-// profiles/r04_kbench_gemm_pp_lean.txt); 1: every dense / im2col tile (the im2col convs keep the round-3 branchy form,
-// which is slower there, and the lean form loses at 128x128 / 1280-wide 16x16 shapes); 3: 256x256 + 256x320 (measured
-// 513.7 vs 508.2 ms/step: off); 0: none
+// irx_set_option("gemm_pp", m): ping-pong main loops.  Non-zero (default 2): the lean dense form on whole 256x256
+// tiles (the 32x32 / 16x16-level GEGLU projections: ff1 -12 / -14 % at the kbench shapes, 49.9 -> 46.5 ms/step in the
+// bench; profiles/r04_kbench_gemm_pp_lean.txt) and the long-K two-source chains of gemm_pp_chain; 0: none (A/B)
 int g_gemm_pp = 2;
 int g_gemm_pp_chain = 1;   // irx_set_option("gemm_pp_chain", 0): the two-source 1x1 chains on the two-stage loop (A/B)
 int g_conv1x1_dense = 1;   // irx_set_option("conv1x1_dense", 0): 1x1 convs on the im2col conv path (A/B)
@@ -323,18 +321,15 @@ bool large_kernel(const GemmArgs& a, const Choice& c, GemmPlan& p) {
     set_kernel(p, 64, 320, 1, 4, 32, 2);
   } else if (c.small) {   // 4 waves, two blocks per CU
     set_kernel(p, 128, c.BN, 2, 2, 64, 2);
-  } else if (g_gemm_deep == 0 &&
-             (!a.A1 || g_gemm_pp_chain) &&   // (two-source A: the lean dense form only, a.conv == 0)
-             (g_gemm_pp == 1 ||
-              (g_gemm_pp >= 2 && !a.conv && !a.ln_out && !a.b_rows &&
-               ((c.BM == 256 && (c.BN == 256 || (g_gemm_pp == 3 && c.BN == 320))) ||
-                // the long-K two-source 1x1 convs (proj_out o ff.net.2 over (h | g), K = 5C): the ping-pong loop pays
-                // where the K loop is long (unlike the K = 320 / 640 projections, which stay on the two-stage loop)
-                (a.A1 && g_gemm_pp_chain && c.BN == 320 && (c.BM == 256 || c.BM == 128) && a.K >= 1024)))) &&
-             (a.conv || (a.M % c.BM == 0 && a.N % c.BN == 0))) {
-    // ping-pong schedule: 3 stages (BK 32 where BK 64 would not fit); dense GEMMs on whole tiles only (the lean form)
-    if (c.BN == 160) return false;
-    set_kernel(p, c.BM, c.BN, wm, wn, (key == 256320 || key == 256256 || key == 128320) ? 32 : 64, 3, 0, true);
+  } else if (g_gemm_deep == 0 && g_gemm_pp && !a.conv && !a.ln_out && !a.b_rows &&
+             (!a.A1 || g_gemm_pp_chain) &&   // (two-source A: the ping-pong loop only where the chain option allows it)
+             ((c.BM == 256 && c.BN == 256) ||
+              // the long-K two-source 1x1 convs (proj_out o ff.net.2 over (h | g), K = 5C): the ping-pong loop pays
+              // where the K loop is long (unlike the K = 320 / 640 projections, which stay on the two-stage loop)
+              (a.A1 && g_gemm_pp_chain && c.BN == 320 && (c.BM == 256 || c.BM == 128) && a.K >= 1024)) &&
+             a.M % c.BM == 0 && a.N % c.BN == 0) {
+    // the lean ping-pong loop: dense GEMMs on whole tiles, 3 stages of BK 32 (BK 64 would not fit these tiles)
+    set_kernel(p, c.BM, c.BN, wm, wn, 32, 3, 0, true);
   } else if (g_gemm_deep == 2) {   // BK 64; a third (fourth) stage wherever it fits in 160 KiB
     if (key == 256320) return false;
     set_kernel(p, c.BM, c.BN, wm, wn, 64, (key == 256256 || key == 128320) ? 2 : key == 128128 ? 4 : 3);
@@ -457,7 +452,7 @@ GemmPlan gemm_plan(const GemmArgs& a) {
   if (a.ln_rs || a.ln_part)
     p.ln_fold = !a.conv && a.alpha == 1.f && one16 && vec_ok(a) && (p.path == GEMM_SK || (p.path == GEMM_LARGE && full_epi));
   // LayerNorm partials out and per-image B / bias: the staged epilogue of the two-stage / lean ping-pong loops
-  const bool staged = p.path == GEMM_LARGE && full_epi && !a.conv && one16 && !a.geglu && g_gemm_pp != 1 && g_gemm_deep == 0;
+  const bool staged = p.path == GEMM_LARGE && full_epi && !a.conv && one16 && !a.geglu && g_gemm_deep == 0;
   if (a.ln_out && g_ln_parts && staged && !a.hs_L && !a.gn_part && a.N % kLnGroup == 0 && !(a.ln_out_rs && a.N != kLnGroup)) {
     // 320-column tiles (the 64x64 / 32x32-level transformer projections).  A call that gemm_sk takes without the
     // partials (option gemm_sk 3) stays there: its consumer runs the statistics pass

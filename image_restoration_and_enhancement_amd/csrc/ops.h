@@ -182,7 +182,7 @@ extern bool g_tile_256x320;
 extern bool g_splitk_inkernel;
 extern int g_gemm_nmajor;   // 0 M-major tile order, 1 N-major where B outweighs A (default), 2 always N-major
 extern int g_gemm_group;   // 1 (default): grouped dense tile order where it cuts per-XCD A + B bytes by > 10 %
-extern int g_gemm_pp;        // 1: ping-pong main loop for dense GEMMs (off: measured slower, see gemm_plan.cpp)
+extern int g_gemm_pp;        // non-zero (default): the lean ping-pong main loop for dense GEMMs on whole 256x256 tiles
 extern int g_gemm_pp_chain;   // 1 (default): the long-K two-source 1x1 chains on the lean dense ping-pong loop
 extern int g_conv1x1_dense;
 extern int g_conv_halo;      // 3x3 convs on whole-row tiles: one LDS halo per 32-channel slab for all 9 taps
@@ -346,7 +346,7 @@ void degrade_jpeg(const uint8_t* img, int B, int H, int W, const int* qt_dev, in
 
 
 // ------------------------------------------------------------ fast non-local means (nlmeans.hip)
-extern int g_nlm_strip, g_nlm_v2, g_nlm2_strip;
+extern int g_nlm2_strip;
 void nlmeans_u8(const uint8_t* src, uint8_t* dst, int N, int H, int W, int ps, int coff, int cn, int tmpl,
                 int search, const int* lut, int lut_len, int shift, hipStream_t s);
 // ------------------------------------------------------------ bilateral / median (filters.hip)

@@ -55,6 +55,14 @@ def test_error_path_without_gpu(lib):
     assert b"option" in h.irx_last_error()
 
 
+def test_retired_options_are_unknown(lib):
+    """The options of the retired NLM variants ("Retired variants") are refused like any unknown name."""
+    h = L.load()
+    for name in (b"nlm_v2", b"nlm_strip"):
+        assert h.irx_set_option(name, 1) != 0, name
+        assert b"unknown option" in h.irx_last_error(), name
+
+
 def test_missing_library_raises(tmp_path):
     with pytest.raises(L.IrxError):
         L.load(tmp_path / "libirx_missing.so", force=True)
