@@ -20,6 +20,7 @@ IRX_LAYOUT_VEC_LN_U, IRX_LAYOUT_VEC_LN_V = 6, 7
 IRX_LAYOUT_MAT_CHAIN, IRX_LAYOUT_VEC_CHAIN = 8, 9
 IRX_LAYOUT_CONV_UP2 = 10
 IRX_RCCL_ID_BYTES = 128   # include/irx.h (sizeof(ncclUniqueId))
+IRX_RESAMPLE_LANCZOS, IRX_RESAMPLE_BICUBIC, IRX_RESAMPLE_MAX_KSIZE = 0, 1, 97
 
 
 class IrxError(RuntimeError):
@@ -124,6 +125,8 @@ _SIGS = {
     "irx_auto_mask_u8": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "irx_colorize_lab_u8": (i32, [vp, vp, i64, vp, vp, vp]),
     "irx_median_blur_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32]),
+    "irx_resample_coeffs": (i32, [i32, i32, i32, vp, vp, i32, C.POINTER(i32)]),
+    "irx_resample_u8": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
     "irx_op_conv2d": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32,
                             i32, i32, i32, vp, i64, vp, vp, i32, i32]),
     "irx_op_gemm": (i32, [vp, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, f32, i32, vp, i64, i32, i32, i64,

@@ -29,7 +29,9 @@ PER_FILE = {"elementwise.hip": ["-ffp-contract=off"],
             "attention.hip": ["-fno-honor-nans"],
             "filters.hip": ["-ffp-contract=off"],
             "degrade.hip": ["-ffp-contract=off"],
-            "degrade_jpeg.hip": ["-ffp-contract=off"]}
+            "degrade_jpeg.hip": ["-ffp-contract=off"],
+            # Pillow's coefficient doubles: libm's sin, IEEE divisions, no FMA (csrc/resample_coeffs.cpp)
+            "resample_coeffs.cpp": ["-ffp-contract=off", "-fno-fast-math"]}
 
 
 def _hipcc() -> str:

@@ -9,7 +9,9 @@ few uint8 levels — parity unpinned (no oracle available), except where stated 
                        integer NLM invoker, exact given the Lab bytes, on 8-bit LBGR-Lab: L with h, the a/b
                        pair with hColor; the GPU form is `nlmeans` / csrc/nlmeans.hip), then
                        bilateralFilter(9, 75, 75) if strength > 0.6 and medianBlur(5) if strength > 0.8.
-* `sr_lanczos`       — src/inference.py:593-596: PIL LANCZOS resize (exact: same library call).
+* `sr_lanczos`       — src/inference.py:593-596: PIL LANCZOS resize (exact: same library call).  On a ROCm device
+                       the drop-in runs the same resize on the GPU, byte for byte (`resample` /
+                       csrc/resample.hip); this host form serves CPU devices.
 * `colorize_lab`     — src/inference.py:683-703: L of RGB->LAB, a = L*0.1-10, b = L*0.1-5 as int8
                        (negative values wrap through the uint8 cast exactly as the reference's
                        `astype(np.uint8)` does), LAB->RGB.

@@ -601,6 +601,19 @@ int irx_median_blur_u8(void* s, const uint8_t* src, uint8_t* dst, int batch, int
   IRX_API_END
 }
 
+// ------------------------------------------------------------------ PIL resize (irx_resample_coeffs: resample_coeffs.cpp)
+int irx_resample_u8(void* s, const uint8_t* src, int batch, int H, int W, int C, const int* xbounds,
+                    const int* xcoeffs, int xk, const int* ybounds, const int* ycoeffs, int yk, int h, int w,
+                    uint8_t* dst) {
+  IRX_API_BEGIN
+  IRX_CHECK(src && dst && src != dst && batch >= 0 && H > 0 && W > 0 && h > 0 && w > 0, "bad arguments");
+  IRX_CHECK(C == 1 || C == 3, "1 or 3 channels");
+  IRX_CHECK((xbounds == nullptr) == (xcoeffs == nullptr) && (ybounds == nullptr) == (ycoeffs == nullptr),
+            "bounds and coeffs: both tables of an axis or neither");
+  IRX_CHECK((xcoeffs || W == w) && (ycoeffs || H == h), "an axis without tables must keep its size");
+  if (batch) resample_u8(src, batch, H, W, C, xbounds, xcoeffs, xk, ybounds, ycoeffs, yk, h, w, dst, S(s));
+  IRX_API_END
+}
 // ------------------------------------------------------------------ single ops
 int irx_op_conv2d(void* s, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hin, int win, int hv,
                   int wv, const void* weight, const float* bias, int cout, int kh, int kw, int stride, int pad_t,

@@ -357,5 +357,8 @@ void auto_mask_u8(const uint8_t* img, int B, int H, int W, uint8_t* mask, uint8_
 void colorize_lab_u8(const uint8_t* img, long npix, const double* lin, const uint8_t* cmap, uint8_t* out,
                      hipStream_t s);
 void median5_u8(const uint8_t* src, uint8_t* dst, int N, int H, int W, int C, hipStream_t s);
+// ------------------------------------------------------------ PIL resize (resample.hip)
+void resample_u8(const uint8_t* src, int B, int H, int W, int C, const int* xb, const int* xc, int xk, const int* yb,
+                 const int* yc, int yk, int h, int w, uint8_t* dst, hipStream_t s);
 
 }  // namespace irx

@@ -1,14 +1,17 @@
-"""Host-side image preparation — diffusers `VaeImageProcessor` semantics.
+"""Image preparation — diffusers `VaeImageProcessor` semantics.
 
-Only the PIL resize runs on the host (the reference does it with PIL too); the uint8 -> [-1, 1]
-conversion and the uint8 post-processing run in `irx_image_to_tensor` / `irx_tensor_to_image`.
+The host forms resize with PIL, as the reference does.  On a ROCm device the same resize runs on the GPU, byte for
+byte (`resample` / csrc/resample.hip): `images_to_device` / `masks_to_device` upload each source image's bytes and
+resize them straight into the engine's batch tensor, and `normalize_mask(..., device=...)` resizes the mask there.
+The uint8 -> [-1, 1] conversion and the uint8 post-processing run in `irx_image_to_tensor` /
+`irx_tensor_to_image`.
 References: img2img preprocess = LANCZOS resize to (W - W%8, H - H%8); inpaint
 image/mask processors resize to 512x512 (A.2); `RestorationPipeline._normalize_mask`
 (`src/inference.py:778-803`).
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 from PIL import Image
@@ -48,10 +51,53 @@ def nearest_downsample(mask: np.ndarray, h: int, w: int) -> np.ndarray:
     return np.ascontiguousarray(mask[..., iy[:, None], ix[None, :]])
 
 
-def normalize_mask(mask: Image.Image, size: Tuple[int, int]) -> Image.Image:
-    """RestorationPipeline._normalize_mask: resize to the image size, invert if < 10 % is white."""
+def images_to_device(images: Sequence[Image.Image], device, height=None, width=None):
+    """`to_uint8` of every image as one device tensor [B, h, w, 3] (same bytes): each image's RGB bytes are
+    uploaded at their own size and resized on the GPU into their slice of the batch.  The images must share the
+    processor's size (h, w); their source sizes may differ when `height` / `width` are given."""
+    import torch
+    from . import resample
+    rgb = [im.convert("RGB") for im in images]
+    sizes = {target_size(im, height, width) for im in rgb}
+    if len(sizes) != 1:
+        raise ValueError(f"images of one batch must share the processed size, got {sorted(sizes)}")
+    h, w = sizes.pop()
+    if h < 1 or w < 1:
+        raise ValueError("height and width must be > 0")
+    out = torch.empty((len(rgb), h, w, 3), dtype=torch.uint8, device=device)
+    for i, im in enumerate(rgb):
+        if resample.supported(im.size, (w, h)):
+            resample.resize_u8(resample.upload(im, device), (w, h), "lanczos", out=out[i])
+        else:                                       # a ratio beyond the kernel's range: Pillow, then the upload
+            out[i].copy_(torch.from_numpy(to_uint8(im, h, w)).to(device))
+    return out
+
+
+def masks_to_device(masks: Sequence[Image.Image], device, height: int, width: int):
+    """`mask_to_binary` of every mask as one device tensor fp32 [B, height, width] of {0, 1}: resized as "L" on
+    the GPU, then `byte >= 128`, which is `byte / 255 >= 0.5` in fp32 for every byte value."""
+    import torch
+    from . import resample
+    out = torch.empty((len(masks), height, width), dtype=torch.float32, device=device)
+    for i, mk in enumerate(masks):
+        m = mk.convert("L")
+        if resample.supported(m.size, (width, height)):
+            u8 = resample.resize_u8(resample.upload(m, device), (width, height), "lanczos")
+            out[i].copy_(u8[..., 0] >= 128)
+        else:
+            out[i].copy_(torch.from_numpy(mask_to_binary(m, height, width)).to(device))
+    return out
+
+
+def normalize_mask(mask: Image.Image, size: Tuple[int, int], device: Optional[str] = None) -> Image.Image:
+    """RestorationPipeline._normalize_mask: resize to the image size, invert if < 10 % is white.  With a ROCm
+    `device` the resize of an "L" / "RGB" mask runs on the GPU (same bytes); other modes stay with Pillow."""
     if mask.size != size:
-        mask = mask.resize(size, Image.LANCZOS)
+        if device is not None and str(device).startswith("cuda"):
+            from . import resample
+            mask = resample.resize_pil(mask, size, "lanczos", device)
+        else:
+            mask = mask.resize(size, Image.LANCZOS)
     a = np.array(mask.convert("L"))
     if np.sum(a > 128) / a.size < 0.1:
         a = 255 - a

@@ -234,20 +234,20 @@ class RestorationPipeline:
         """Same-size RGB PIL images -> restored PIL images (size rounded down to a multiple of 8)."""
         if prompt is None:
             raise ValueError("Provide either `prompt` or `prompt_embeds`.")
-        u8 = np.stack([ip.to_uint8(im.convert("RGB")) for im in images])
-        if u8.shape[1] < 8 or u8.shape[2] < 8:
+        # each image's bytes are uploaded as they are and snapped to a multiple of 8 on the device (same bytes as
+        # ip.to_uint8: tests/test_resample_wiring_gpu.py)
+        dev = ip.images_to_device(images, self.device)
+        if dev.shape[1] < 8 or dev.shape[2] < 8:
             raise ValueError(f"image too small for the VAE: {images[0].size}")
-        dev = torch.from_numpy(u8).to(self.device).contiguous()
         res = model.engine.img2img(dev, prompt, strength, steps, guidance, seed=self.seed)
         return [Image.fromarray(a) for a in res.images_u8.cpu().numpy()]
 
     def _inpaint_native(self, model: NativeSDModel, images: Sequence[Image.Image], masks: Sequence[Image.Image],
                         prompt: str, strength: float, steps: int, guidance: float) -> List[Image.Image]:
         S = INPAINT_SIZE
-        u8 = np.stack([ip.to_uint8(im.convert("RGB"), S, S) for im in images])
-        m = np.stack([ip.mask_to_binary(mk, S, S) for mk in masks])
-        res = model.engine.inpaint(torch.from_numpy(u8).to(self.device).contiguous(),
-                                   torch.from_numpy(m).to(self.device).contiguous(), prompt, strength, steps,
+        # images (of any size) and masks are squashed to 512x512 on the device; the mask is binarised there
+        res = model.engine.inpaint(ip.images_to_device(images, self.device, S, S),
+                                   ip.masks_to_device(masks, self.device, S, S), prompt, strength, steps,
                                    guidance, seed=self.seed)
         return [Image.fromarray(a) for a in res.images_u8.cpu().numpy()]
 
@@ -287,16 +287,21 @@ class RestorationPipeline:
         return self._sr_lanczos(image, scale=scale)
 
     @staticmethod
-    def _cap_area(image: Image.Image) -> Image.Image:
+    def _cap_area(image: Image.Image, device: Optional[str] = None) -> Image.Image:
+        """SR's area cap (src/inference.py:552-559); with a ROCm `device` the resize runs on the GPU (same bytes)."""
         w, h = image.size
         if w * h > 1024 * 1024:
             new_w, new_h = (1024, int(h * 1024 / w)) if w > h else (int(w * 1024 / h), 1024)
-            image = image.resize((new_w, new_h), Image.LANCZOS)
+            if device is not None and str(device).startswith("cuda"):
+                from . import resample
+                image = resample.resize_pil(image, (new_w, new_h), Image.LANCZOS, device)
+            else:
+                image = image.resize((new_w, new_h), Image.LANCZOS)
         return image
 
     def _sr_sd(self, image: Image.Image, model, scale: int, **kwargs) -> Image.Image:
         try:
-            image = self._cap_area(image)
+            image = self._cap_area(image, self.device)
             prompt = kwargs.get("prompt", self.prompts["sr"])
             s, steps, g = SD_PARAMS["sr"]
             return self._img2img(model, [image], prompt, s, steps, g)[0]
@@ -307,6 +312,10 @@ class RestorationPipeline:
             return self._sr_lanczos(image, scale=scale)
 
     def _sr_lanczos(self, image: Image.Image, scale: int) -> Image.Image:
+        if self.device.startswith("cuda"):         # the same PIL LANCZOS resize, on the GPU (same bytes)
+            from . import resample
+            w, h = image.size
+            return resample.resize_pil(image, (w * scale, h * scale), Image.LANCZOS, self.device)
         return classical.sr_lanczos(image, scale)
 
     # ------------------------------------------------------------------------------------ colorize
@@ -398,7 +407,7 @@ class RestorationPipeline:
             return image
 
     def _normalize_mask(self, mask: Image.Image, target_size: tuple[int, int]) -> Image.Image:
-        return ip.normalize_mask(mask, target_size)
+        return ip.normalize_mask(mask, target_size, self.device)
 
     def _auto_mask_from_image(self, image: Image.Image) -> Image.Image | None:
         if self.device.startswith("cuda"):         # threshold + close + open + count on the GPU
@@ -478,7 +487,7 @@ class RestorationPipeline:
                     continue
                 im = self.gray_to_rgb(im)
             if task == "sr":
-                im = self._cap_area(im)
+                im = self._cap_area(im, self.device)
             if task == "inpaint":
                 if mk is None:
                     out[i] = single(im, mk)

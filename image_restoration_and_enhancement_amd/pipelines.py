@@ -6,7 +6,8 @@ makes at `src/inference.py:486-495, :566-573, :664-672, :758-767` — for a batc
 share a prompt.  Everything between the uint8 input pixels and the uint8 output pixels runs on the
 GPU through libirx: pixel normalisation, VAE encode, posterior sampling + add_noise, CLIP text
 encoding, the denoising loop (UNet + fused CFG/scheduler/pack step kernel), VAE decode and the
-uint8 post-processing.  The host only resizes with PIL, draws the seeded noise (CPU
+uint8 post-processing.  The PIL resize in front of it runs on the GPU too (`resample`, called by
+`image_processor.images_to_device` / `masks_to_device`).  The host only draws the seeded noise (CPU
 `torch.Generator`, exactly like the reference on a CPU device) and plans scheduler coefficients.
 
 Every image gets the noise of a fresh `Generator.manual_seed(seed)`, because the reference

@@ -271,6 +271,27 @@ int irx_colorize_lab_u8(void* stream, const uint8_t* img, long npix, const doubl
 /* cv2.medianBlur(img, 5) on uint8 [batch][H][W][C], C <= 4 (src != dst). */
 int irx_median_blur_u8(void* stream, const uint8_t* src, uint8_t* dst, int batch, int H, int W, int C, int ksize);
 
+/* ---- PIL `Image.resize(size, LANCZOS | BICUBIC)` on 8-bit images, byte for byte (Pillow's ImagingResample): the
+ * LANCZOS fallback of super-resolution (src/inference.py:593-596), the SR area cap (:552-559), the mask resize of
+ * _normalize_mask (:790-801) and the VaeImageProcessor resize of the img2img / inpaint preprocess (SURVEY.md A.1 /
+ * A.2: to a multiple of 8, to 512x512, the inpaint mask as "L").  `box` / `reducing_gap` and modes with alpha
+ * (premultiplied by Pillow) are not covered. ---- */
+#define IRX_RESAMPLE_LANCZOS 0
+#define IRX_RESAMPLE_BICUBIC 1
+#define IRX_RESAMPLE_MAX_KSIZE 97   /* per axis, what irx_resample_u8 accepts: LANCZOS down to 1/16 */
+/* Host only: one axis' tables for in_size -> out_size.  bounds[out_size][2] = (first source index, taps n),
+ * coeffs[out_size][ksize] = the 22-bit fixed-point weights (entries from n on are 0); cap = capacity of `coeffs`
+ * in ints.  Null table pointers: sizes only.  Writes *ksize (any ratio; the kernel's limit is checked there). */
+int irx_resample_coeffs(int in_size, int out_size, int filter, int* bounds, int* coeffs, int cap, int* ksize);
+/* uint8 [batch][H][W][C] -> [batch][h][w][C], C = 1 or 3, src != dst; the tables are device copies of
+ * irx_resample_coeffs' (x: W -> w, y: H -> h).  Horizontal pass first, its result rounded to uint8 as Pillow's
+ * temporary image, then the vertical pass; null x tables with W == w skip the horizontal pass, null y tables with
+ * H == h the vertical one (both: a copy).  One fused kernel, no allocation.  xk or yk above
+ * IRX_RESAMPLE_MAX_KSIZE: a status, nothing launched. */
+int irx_resample_u8(void* stream, const uint8_t* src, int batch, int H, int W, int C, const int* xbounds,
+                    const int* xcoeffs, int xk, const int* ybounds, const int* ycoeffs, int yk, int h, int w,
+                    uint8_t* dst);
+
 /* ---- multi-GPU: RCCL over xGMI (SURVEY.md §8b `irx_weights_bcast(handle, rcclComm)`, §8e) ----
    The reference has no multi-device path (src/inference.py:52-57 picks one device; it stands in for
    `pipe.to("cuda")` at src/inference.py:175-176 on every rank but the first).  One process per GPU: rank 0
