@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/irx.h"
+#include "gemm_plan.h"
 #include "models.h"
 #include "profile.h"
 
@@ -95,6 +96,7 @@ static const struct { const char* name; int* i; bool* b; } kOpts[] = {
     {"halo_split", &g_halo_split, nullptr},
     {"halo_pipe", &g_halo_pipe, nullptr},
     {"gemm_pp", &g_gemm_pp, nullptr},
+    {"gemm_pp2", &g_gemm_pp2, nullptr},
     {"ln_fold", &g_ln_fold, nullptr},
     {"gemm_sk", &g_gemm_sk, nullptr},
     {"large_mask", &g_large_mask, nullptr},
@@ -681,6 +683,29 @@ size_t irx_op_gemm_workspace_bytes(int dtype, int M, int N, int K, int act, int 
   a.C = (void*)(uintptr_t)4096; a.ldc = N;
   a.act = act; a.out_f32 = out_f32; a.imgs = imgs;
   return gemm_workspace_bytes(a);
+}
+
+// (tests, scripts/kbench.py; not part of irx.h) the large-tile kernel the planner gives a dense 16-bit GEMM, or a fused
+// GEGLU projection, of this shape under the current options: tile = {BM, BN, ping-pong loop, blocks per CU it is built
+// for, group_m}, zeros when another kernel runs the call
+int irx_debug_gemm_tile(int dtype, int M, int N, int K, int geglu, int imgs, int* tile) {
+  IRX_API_BEGIN
+  IRX_CHECK(tile, "null argument");
+  GemmArgs a;
+  a.dtype = dtype; a.M = M; a.N = N; a.K = K;
+  a.A = (const void*)(uintptr_t)4096; a.lda = K;   // (aligned stand-ins, never read)
+  a.B = (const void*)(uintptr_t)4096; a.ldb = K;
+  a.C = (void*)(uintptr_t)4096; a.ldc = geglu ? N / 2 : N;
+  a.geglu = geglu ? 1 : 0;
+  a.imgs = imgs;
+  const GemmPlan p = gemm_plan(a);
+  const bool lt = p.path == GEMM_LARGE;
+  tile[0] = lt ? p.BM : 0;
+  tile[1] = lt ? p.BN : 0;
+  tile[2] = lt && p.PP;
+  tile[3] = !lt ? 0 : (p.PP && p.BM * p.BN == 256 * 128) || p.WM * p.WN == 4 ? 2 : 1;
+  tile[4] = lt ? p.group_m : 0;
+  IRX_API_END
 }
 
 int irx_op_group_norm(void* s, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hw, int groups,

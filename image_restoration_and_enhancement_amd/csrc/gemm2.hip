@@ -114,10 +114,23 @@ __device__ __forceinline__ void glds16_s(uint32_t voff, const void* base, uint32
 constexpr int kStripEdgeL = 320, kStripEdgeR = 336;
 static_assert(kStripEdgeR + 16 <= 256 + 2 * kHaloWMax, "strip halo edge columns");
 
+// The ping-pong loop on 256x128 / 128x256 tiles (72 KiB of LDS): built for two resident 8-wave blocks per CU
+constexpr bool pp_pair(bool pp, int bm, int bn) { return pp && bm * bn == 256 * 128; }
+
+// (__launch_bounds__' second argument is the minimum number of waves per SIMD: an 8-wave block puts 2 on each SIMD, so
+//  4 asks for two resident blocks, i.e. at most 128 VGPRs; the 4-wave blocks ask for 2 = two blocks per CU)
 template <typename T, int BM, int BN, int WM, int WN, int BK, int S, bool CONV, bool OUTF32, bool RESIZE,
           int HALO = 0, bool PP = false>
-__global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void gemm2_kernel(GemmArgs a, Split sp) {
-  constexpr int NW = WM * WN, NT = NW * 64;   // 8 waves (1 block/CU) or 4 waves (2 blocks/CU)
+__global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 4 ? 2 : 1) void gemm2_kernel(GemmArgs a,
+                                                                                                            Split sp) {
+  constexpr int NW = WM * WN, NT = NW * 64;   // 8 waves (2 waves per SIMD) or 4 waves (1 per SIMD, 2 blocks/CU)
+  // PAIR tiles take (host: pair_form, gemm_plan.cpp) one A source, one K split, shared weights, and no row add, GroupNorm /
+  // LayerNorm partials or sub-pixel rows: those forms are compile-time dead here, which keeps the epilogue in 128 VGPRs
+  constexpr bool PAIR = pp_pair(PP, BM, BN);
+  if constexpr (PAIR) {
+    a.A1 = nullptr; a.b_rows = 0; a.rowadd = nullptr; a.gn_part = nullptr; a.ln_out = nullptr; a.up2_w = 0;
+    sp.splits = 1;
+  }
   constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
   constexpr int ROWS = BM + BN;
   constexpr int CPR = BK / 8;                // 16-byte chunks per row per stage
@@ -1654,6 +1667,9 @@ void gemm_large_tile(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
     IRX_K2(256, 320, 2, 4, 32, 3, 0, true)
     IRX_K2(256, 256, 2, 4, 32, 3, 0, true)
     IRX_K2(128, 320, 2, 4, 32, 3, 0, true)
+    // ... and two resident blocks per CU (option gemm_pp2)
+    IRX_K2(256, 128, 4, 2, 32, 3, 0, true)
+    IRX_K2(128, 256, 2, 4, 32, 3, 0, true)
     // option gemm_deep 2: BK-64 rings of three / four stages (256x256 / 128x320 fit two: the two-stage loop below)
     IRX_K2(256, 128, 4, 2, 64, 3, 0, false)
     IRX_K2(128, 256, 2, 4, 64, 3, 0, false)

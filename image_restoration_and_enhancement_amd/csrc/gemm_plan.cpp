@@ -26,11 +26,17 @@ int g_gemm_force = 0;            // irx_set_option("gemm_force", BM*100000 + BN*
 bool g_tile_256x320 = true;      // irx_set_option("tile_256x320", 0): no 256x320 tiles (A/B)
 bool g_splitk_inkernel = true;   // irx_set_option("splitk_inkernel", 0): separate split-K reduce kernel (A/B)
 int g_gemm_nmajor = 1;   // 0 M-major tile order, 1 N-major where B outweighs A (default), 2 always N-major
-int g_gemm_group = 1;    // irx_set_option("gemm_group", 0): the M-major / N-major dense tile orders only (A/B)
+int g_gemm_group = 1;    // irx_set_option("gemm_group", 0): the M-major / N-major dense tile orders only (A/B);
+                         // g >= 2: groups of g M tiles whatever the cost model says (tests)
 // irx_set_option("gemm_pp", m): ping-pong main loops.  Non-zero (default 2): the lean dense form on whole 256x256
 // tiles (the 32x32 / 16x16-level GEGLU projections: ff1 -12 / -14 % at the kbench shapes, 49.9 -> 46.5 ms/step in the
 // bench; profiles/r04_kbench_gemm_pp_lean.txt) and the long-K two-source chains of gemm_pp_chain; 0: none (A/B)
 int g_gemm_pp = 2;
+// irx_set_option("gemm_pp2", m): the lean ping-pong loop on 256x128 / 128x256 tiles built for two resident 8-wave
+// blocks per CU (72 KiB of LDS, <= 128 VGPRs): one block's ring fill, load waits and epilogue run beside the other's
+// MFMA phases.  1 (default): the shapes of pair_tile() below; 0: none (A/B); 2 / 3: 256x128 / 128x256 wherever the
+// kernel's conditions hold (kbench, tests: also K % 32 == 0 instead of K % 64 == 0)
+int g_gemm_pp2 = 1;
 int g_gemm_pp_chain = 1;   // irx_set_option("gemm_pp_chain", 0): the two-source 1x1 chains on the two-stage loop (A/B)
 int g_conv1x1_dense = 1;   // irx_set_option("conv1x1_dense", 0): 1x1 convs on the im2col conv path (A/B)
 int g_conv_halo = 1;     // irx_set_option("conv_halo", m): 0 im2col walk for every conv (A/B),
@@ -54,11 +60,13 @@ int g_ln_parts = 1;      // 1: transformer producers emit LayerNorm partials, th
 namespace {
 
 constexpr int kCUs = 256;
+constexpr long kPairMinTiles = 2L * kCUs;   // two pair tiles (option gemm_pp2) per CU
 
 struct Choice {
   int BM = 0, BN = 0, splits = 1, per = 0;
   bool small = false;   // 4-wave block, two resident per CU (short-K GEMMs: one block's prologue/epilogue
                         // overlaps the other's MFMA loop)
+  bool pair = false;    // 8-wave ping-pong block, two resident per CU (pair_tile)
 };
 
 int step_k() { return g_gemm_deep == 1 ? 32 : 64; }   // K depth of one pipeline stage (eligibility granule)
@@ -76,7 +84,7 @@ bool reduce_in_kernel(int splits, long tiles) { return g_splitk_inkernel && spli
 
 Choice choose(const GemmArgs& a) {
   Choice best;
-  const int nk = a.K / step_k();
+  const int nk = std::max(1, a.K / step_k());   // (K < 64: the forced pair tiles of option gemm_pp2 only)
   if (g_gemm_small && g_gemm_deep == 0 && a.K <= g_gemm_small_kmax) {
     const int bn = (!a.geglu && a.N % 160 == 0) ? 160 : (a.N % 128 == 0 ? 128 : 0);
     if (bn) {
@@ -138,8 +146,38 @@ bool vec_ok(const GemmArgs& a) {
          (a.batch == 1 || (a.sC % 8 == 0 && (!a.residual || a.sR % 8 == 0)));
 }
 
+// What the two-per-CU ping-pong tiles (gemm2.hip, PAIR) compile out or never handle: convs, a second A source, K
+// splits (the caller checks), per-image weights, row add, GroupNorm / LayerNorm partials, sub-pixel rows
+bool pair_form(const GemmArgs& a) {
+  return g_gemm_pp2 && g_gemm_pp && g_gemm_deep == 0 && !g_gemm_small && g_gemm_force == 0 && !a.conv && !a.A1 &&
+         !a.b_rows && !a.rowadd && !a.gn_part && !a.gn_ab && !a.ln_out && !a.up2_w && a.K % 32 == 0;
+}
+
+// The pair tile (BM, BN) that replaces the choice `c` of a dense GEMM, or false.  A function of the canonical shape
+// only (canon_rows, N, K, feature flags), never of the actual batch.
+bool pair_tile(const GemmArgs& a, const Choice& c, int& BM, int& BN) {
+  if (!pair_form(a)) return false;
+  int bm = 256, bn = 128;   // (BM 256: the per-image row tile rules of the fused GEGLU / LayerNorm fold read as before)
+  if (g_gemm_pp2 >= 2) {    // (forced: one K split whatever `choose` gave)
+    if (g_gemm_pp2 == 3) { bm = 128; bn = 256; }
+  } else {
+    // the shapes that won their kbench: the fused GEGLU projections `choose` gave 256x256 tiles, from
+    // one tile per CU (the GELU pass is the VALU work the partner block hides); the wide K >= 640 projections on
+    // 128x320 tiles (q|k|v at 32^2) from two per CU.  Plain 256x256 calls (q|k|v at 16^2) did not resolve, N = 640
+    // with 1.25 tiles per CU lost: both stay
+    if (c.splits != 1 || a.K % 64 != 0) return false;
+    const long tiles = canon_rows(a) / bm * (a.N / bn);
+    const bool geglu = a.geglu && c.BM == 256 && c.BN == 256 && tiles >= kCUs;
+    const bool wide = !a.geglu && c.BM == 128 && c.BN == 320 && a.K >= 640 && tiles >= kPairMinTiles;
+    if (!geglu && !wide) return false;
+  }
+  if (a.M % bm != 0 || a.N % bn != 0) return false;
+  BM = bm; BN = bn;
+  return true;
+}
+
 bool eligible(const GemmArgs& a) {
-  const int bk = step_k();
+  const int bk = (g_gemm_pp2 >= 2 && pair_form(a)) ? 32 : step_k();
   if (!(g_large_mask & (a.conv ? 2 : 1))) return false;   // (A/B: large tiles for dense GEMMs / convs only)
   if (!a.conv && g_large_dense != 63) {   // (diagnostics: dense classes on large tiles)
     const int cls = a.geglu ? (a.K <= 320 ? 4 : a.K <= 640 ? 16 : 32) : a.hs_L ? 2 : a.N <= 1280 ? 1 : 8;
@@ -267,6 +305,7 @@ int dense_group_m(const GemmArgs& a, int bm, int bn, int resident, bool nmajor) 
   if (!g_gemm_group) return 0;
   const long tiles_m = (a.M + bm - 1) / bm, tiles_n = (a.N + bn - 1) / bn;
   if (tiles_n < 2 || tiles_m < 2) return 0;
+  if (g_gemm_group >= 2) return (int)std::min((long)g_gemm_group, tiles_m);
   const long q = (tiles_m * tiles_n + 7) / 8, w = std::min(q, 32L * resident);
   const double a_m = (double)bm * a.K * 2.0, b_n = (double)bn * a.K * 2.0;
   auto cost = [&](long g) {
@@ -317,7 +356,9 @@ void plan_halo_launch(const GemmArgs& a, const Halo& h, GemmPlan& p) {
 bool large_kernel(const GemmArgs& a, const Choice& c, GemmPlan& p) {
   const int key = c.BM * 1000 + c.BN;
   const int wm = (c.BM == 256 && c.BN <= 160) ? 4 : 2, wn = 8 / wm;   // 256x128 / 256x160: 4 x 2 waves
-  if (c.BM == 64) {   // 64x320, 4 waves, BK 32, two stages (48 KiB of LDS: three blocks per CU)
+  if (c.pair) {   // the lean ping-pong loop, two 8-wave blocks per CU (pair_tile)
+    set_kernel(p, c.BM, c.BN, wm, wn, 32, 3, 0, true);
+  } else if (c.BM == 64) {   // 64x320, 4 waves, BK 32, two stages (48 KiB of LDS: three blocks per CU)
     set_kernel(p, 64, 320, 1, 4, 32, 2);
   } else if (c.small) {   // 4 waves, two blocks per CU
     set_kernel(p, 128, c.BN, 2, 2, 64, 2);
@@ -345,7 +386,14 @@ bool large_kernel(const GemmArgs& a, const Choice& c, GemmPlan& p) {
 
 // A dense / im2col GEMM on the large tiles `c`; false, with `p` untouched (the 4-wave kernel runs), where the epilogue
 // forms do not fit
-bool plan_large(const GemmArgs& a, const Choice& c, GemmPlan& p) {
+bool plan_large(const GemmArgs& a, const Choice& c0, GemmPlan& p) {
+  Choice c = c0;
+  if (pair_tile(a, c0, c.BM, c.BN)) {
+    c.pair = true;
+    c.splits = 1;
+  } else if (a.K % step_k() != 0) {   // (eligible() let K % 32 == 0 through for the forced pair tiles only)
+    return false;
+  }
   const bool vec = vec_ok(a);
   if (a.geglu && !vec) return false;
   if (c.splits > 1) {
@@ -359,12 +407,12 @@ bool plan_large(const GemmArgs& a, const Choice& c, GemmPlan& p) {
   // XCD's consecutive tiles re-use one B panel from its L2 instead of every XCD streaming all of B
   p.nmajor = g_gemm_nmajor == 2 || (g_gemm_nmajor == 1 && (long)a.N * a.batch > (long)a.M * a.batch);
   if (a.batch == 1 && !a.hs_L) {   // grouped order where it cuts an XCD's co-resident A + B bytes (GemmArgs::group_m)
-    p.group_m = dense_group_m(a, c.BM, c.BN, (c.BM == 128 && c.BN == 128) || c.small ? 2 : 1, p.nmajor);
+    p.group_m = dense_group_m(a, c.BM, c.BN, (c.BM == 128 && c.BN == 128) || c.small || c.pair ? 2 : 1, p.nmajor);
     if (p.group_m) p.nmajor = 0;
   }
   p.splits = c.splits;
   // K steps per split: the choice counts steps of step_k(), the kernel steps of its BK
-  p.per = (c.splits > 1 ? c.per : a.K / step_k()) * (step_k() / p.BK);
+  p.per = c.pair ? a.K / p.BK : (c.splits > 1 ? c.per : a.K / step_k()) * (step_k() / p.BK);
   if (c.splits > 1) {
     p.Mp = (a.M + c.BM - 1) / c.BM * c.BM;
     p.Np = (a.N + c.BN - 1) / c.BN * c.BN;

@@ -183,6 +183,7 @@ extern bool g_splitk_inkernel;
 extern int g_gemm_nmajor;   // 0 M-major tile order, 1 N-major where B outweighs A (default), 2 always N-major
 extern int g_gemm_group;   // 1 (default): grouped dense tile order where it cuts per-XCD A + B bytes by > 10 %
 extern int g_gemm_pp;        // non-zero (default): the lean ping-pong main loop for dense GEMMs on whole 256x256 tiles
+extern int g_gemm_pp2;       // the ping-pong loop on 256x128 / 128x256 tiles, two resident blocks per CU (gemm_plan.cpp)
 extern int g_gemm_pp_chain;   // 1 (default): the long-K two-source 1x1 chains on the lean dense ping-pong loop
 extern int g_conv1x1_dense;
 extern int g_conv_halo;      // 3x3 convs on whole-row tiles: one LDS halo per 32-channel slab for all 9 taps

@@ -93,6 +93,8 @@ def main():
     ap.add_argument("--variants", default="s2,ring64,small")
     ap.add_argument("--attn-qrep", action="store_true", help="cross-attention: sweep the resident-K/V query groups")
     ap.add_argument("--pf80", action="store_true", help="d = 80 self-attention: option attn_pf80 on / off")
+    ap.add_argument("--pair", action="store_true", help="the GEGLU / q|k|v projections with the LayerNorm fold: the default "
+                    "kernel vs the two-per-CU ping-pong tiles (option gemm_pp2), alternated, two repeats")
     ap.add_argument("--lnout", action="store_true", help="residual-stream producers with / without LayerNorm partials")
     args = ap.parse_args()
     dev = torch.device("cuda")
@@ -100,10 +102,12 @@ def main():
     dt = torch.bfloat16
     g = torch.Generator(device=dev).manual_seed(0)
     base = {"large_tiles": 1, "gemm_deep": 0, "gemm_small": 0, "tile_256x320": 1, "splitk_inkernel": 1, "halo_pipe": 1,
-            "gemm_pp": 0, "gemm_force": 0, "gemm_dbg": 0}
+            "gemm_pp": 0, "gemm_pp2": 0, "gemm_force": 0, "gemm_dbg": 0}
     allv = {"s2": {}, "ring64": {"gemm_deep": 2}, "ring32": {"gemm_deep": 1}, "small": {"gemm_small": 1}, "4wave": {"large_tiles": 0},
             "no320": {"tile_256x320": 0}, "redk": {"splitk_inkernel": 0}, "no320redk": {"tile_256x320": 0, "splitk_inkernel": 0},
             "halo1": {"halo_pipe": 0}, "halo2": {"halo_pipe": 1}, "pp0": {"gemm_pp": 0}, "pp2": {"gemm_pp": 2},
+            # two resident ping-pong blocks per CU: 256x128 / 128x256 tiles forced (option gemm_pp2 2 / 3)
+            "pair256x128": {"gemm_pp": 2, "gemm_pp2": 2}, "pair128x256": {"gemm_pp": 2, "gemm_pp2": 3},
             "nm0": {"gemm_nmajor": 0},
             # timing diagnostics (results wrong): 1 no epilogue, 2 no MFMAs, 3 neither
             "dbg1": {"gemm_dbg": 1}, "dbg2": {"gemm_dbg": 2}, "dbg3": {"gemm_dbg": 3},
@@ -115,6 +119,39 @@ def main():
     def setv(opts):
         for k, v in {**base, **opts}.items():
             L.call("irx_set_option", k.encode(), v)
+    if args.pair:   # the folded-LayerNorm projections of the bench step (M at 16 images), per shape: repeats x variants
+        import ctypes as C
+        setv({})
+        for lab, M, N, K, geglu in (("geglu@32", 16384, 5120, 640, 1), ("geglu@16", 4096, 10240, 1280, 1),
+                                    ("qkv@16", 4096, 3840, 1280, 0), ("geglu@64", 65536, 2560, 320, 1),
+                                    ("qkv@32", 16384, 1920, 640, 0), ("geglu@8", 1024, 10240, 1280, 1),
+                                    ("lin640@32", 16384, 640, 640, 0)):
+            if args.match not in lab:
+                continue
+            A = torch.randn(M, K, device=dev, generator=g).to(dt)
+            Bw = (torch.randn(N, K, device=dev, generator=g) / math.sqrt(K)).to(dt)
+            u = Bw.float().sum(1).contiguous()
+            v = torch.zeros(N, device=dev)
+            Af = A.float()
+            mean = Af.mean(-1)
+            rstd = torch.rsqrt(Af.var(-1, unbiased=False) + 1e-5)
+            rs = torch.stack([rstd, rstd * mean], -1).contiguous()
+            out = torch.empty(M, N // 2 if geglu else N, dtype=dt, device=dev)
+            flops = 2.0 * M * N * K
+            # (gemm_sk 1: the K = 320 GEGLU's default kernel; the pair tiles need it off to reach the planner)
+            runs = (("default", {"gemm_pp2": 0, "gemm_sk": 1}), ("pair256x128", {"gemm_pp2": 2, "gemm_sk": 0}),
+                    ("pair128x256", {"gemm_pp2": 3, "gemm_sk": 0}))
+            res = []
+            for rep in range(2):
+                for vn, opts in runs:
+                    with L.option(gemm_pp=2, **opts):
+                        tile = (C.c_int * 5)()
+                        L.load().irx_debug_gemm_tile(O.DT[dt], M, N, K, geglu, 16, tile)
+                        ms = timeit(lambda: L.call("irx_op_gemm_ln_fold", O.S(), O.DT[dt], M, N, K, O.P(A), O.P(Bw), O.P(u),
+                                                   O.P(v), O.P(rs), None, 0, geglu, O.P(out)), args.iters)
+                    res.append(f"{vn}[{tile[0]}x{tile[1]}/{tile[3]}] {ms * 1e3:7.1f}us {flops / ms / 1e9:6.1f}TF")
+            print(f"{lab:10s} M{M} N{N} K{K} " + " | ".join(res), flush=True)
+        return
     if args.only in ("", "conv"):
         for lab, N, H, W, C0, C1, Co, k, s, up in CONVS:
             if args.match not in lab:
