@@ -902,6 +902,140 @@ int irx_op_gemm_geglu(void* s, int dtype, int M, int N, int K, const void* A, co
   IRX_API_END
 }
 
+// ---- GroupNorm statistics from producer partials (GemmArgs::gn_part): the producers as the models run them, and the
+// consumers on their own.  A producer call with out == NULL is a shape-only query (nothing launched).
+namespace {
+// Model::run_gemm's part: the partials go out when the call's epilogue emits them in row blocks that divide an image;
+// split-K partials come from the caller's workspace.  *halo = the halo main loop the plan launches (0: not a halo conv).
+void gn_producer_plan(GemmArgs& a, long rows_per_image, double* parts, int* rows, int* splits, int* halo,
+                      size_t* ws_bytes) {
+  const int r = gemm_emits_gn_parts(a);
+  *rows = (r > 0 && rows_per_image > 0 && rows_per_image % r == 0) ? r : 0;
+  if (*rows) a.gn_part = parts ? parts : (double*)(uintptr_t)4096;   // (query: a stand-in, never written)
+  const GemmPlan p = gemm_plan(a);
+  *splits = p.large() ? p.splits : 0;
+  *halo = p.path == GEMM_HALO ? p.HALO : 0;
+  *ws_bytes = p.ws_reserve;
+}
+}  // namespace
+
+int irx_op_conv2d_gn_parts(void* s, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hin, int win,
+                           int hv, int wv, const void* weight, const float* bias, int cout, int kh, int kw, int stride,
+                           int pad_t, int pad_l, int ho, int wo, const float* rowadd, long rowadd_ld,
+                           const void* residual, void* out, int out_f32, int act, double* parts, void* ws, int* rows,
+                           int* splits, int* halo, size_t* ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(rows && splits && halo && ws_bytes, "null argument");
+  GemmArgs a;
+  a.dtype = dtype;
+  a.conv = 1;
+  a.g.src0 = x0; a.g.src1 = x1; a.g.C0 = c0; a.g.C1 = c1;
+  a.g.N = n; a.g.Hin = hin; a.g.Win = win; a.g.Hv = hv; a.g.Wv = wv;
+  a.g.KH = kh; a.g.KW = kw; a.g.stride = stride; a.g.pad_t = pad_t; a.g.pad_l = pad_l; a.g.Ho = ho; a.g.Wo = wo;
+  a.M = n * ho * wo; a.N = cout; a.K = kh * kw * (c0 + c1);
+  a.B = weight; a.ldb = a.K;
+  a.C = out ? out : (void*)(uintptr_t)4096; a.ldc = cout; a.out_f32 = out_f32;   // (query: an aligned stand-in)
+  a.bias = bias;
+  a.rowadd = rowadd; a.rowadd_ld = rowadd_ld; a.rows_per_group = ho * wo;
+  a.residual = residual; a.ldr = cout;
+  a.act = act;
+  a.imgs = n;
+  conv1x1_as_dense(a);   // as irx_op_conv2d and the models do
+  gn_producer_plan(a, (long)ho * wo, out ? parts : nullptr, rows, splits, halo, ws_bytes);
+  if (!out) return 0;
+  IRX_CHECK(!*rows || parts, "this call emits GroupNorm partials: give the buffer");
+  IRX_CHECK(ws || !*ws_bytes, "split-K workspace missing");
+  a.splitk_ws = ws;
+  a.splitk_ws_bytes = *ws_bytes;
+  gemm(a, S(s));
+  IRX_API_END
+}
+
+int irx_op_gemm_gn_parts(void* s, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,
+                         const void* residual, int imgs, void* C, double* parts, void* ws, int* rows, int* splits,
+                         size_t* ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(rows && splits && ws_bytes, "null argument");
+  IRX_CHECK(imgs > 0 && M % imgs == 0, "rows must be whole images");
+  GemmArgs a;   // Model::linear's form
+  a.dtype = dtype; a.M = M; a.N = N; a.K = K;
+  a.A = A ? A : (const void*)(uintptr_t)4096; a.lda = K;
+  a.B = B; a.ldb = K;
+  a.C = C ? C : (void*)(uintptr_t)4096; a.ldc = N;
+  a.bias = bias;
+  a.residual = residual; a.ldr = N;
+  a.imgs = imgs;
+  int halo = 0;
+  gn_producer_plan(a, M / imgs, C ? parts : nullptr, rows, splits, &halo, ws_bytes);
+  if (!C) return 0;
+  IRX_CHECK(!*rows || parts, "this call emits GroupNorm partials: give the buffer");
+  IRX_CHECK(ws || !*ws_bytes, "split-K workspace missing");
+  a.splitk_ws = ws;
+  a.splitk_ws_bytes = *ws_bytes;
+  gemm(a, S(s));
+  IRX_API_END
+}
+
+int irx_op_upsample_conv_gn_parts(void* s, int dtype, const void* x, int n, int h, int w, int c, const void* w2,
+                                  const float* bias, void* out, double* parts, void* ws, int* up2_ok, int* rows,
+                                  size_t* ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(up2_ok && rows && ws_bytes, "null argument");
+  GemmArgs a;   // Model::upsample_conv's per-parity 2x2 conv over the low-resolution pixels
+  a.dtype = dtype;
+  a.conv = 1;
+  a.g.src0 = x; a.g.C0 = c;
+  a.g.N = n; a.g.Hin = h; a.g.Win = w; a.g.Hv = h; a.g.Wv = w;
+  a.g.KH = 2; a.g.KW = 2; a.g.stride = 1; a.g.pad_t = 1; a.g.pad_l = 1; a.g.Ho = h; a.g.Wo = w;
+  a.M = n * h * w; a.N = c; a.K = 4 * c;
+  a.B = w2; a.ldb = a.K;
+  a.C = out ? out : (void*)(uintptr_t)4096; a.ldc = c;   // (query: an aligned stand-in, never written)
+  a.bias = bias;
+  a.rows_per_group = h * w;
+  a.ldr = c;
+  a.imgs = n;
+  a.up2_h = h; a.up2_w = w;
+  *up2_ok = gemm_up2_ok(a) ? 1 : 0;
+  const int r = *up2_ok ? gemm_emits_gn_parts(a) : 0;
+  *rows = (r > 0 && ((long)h * w) % r == 0) ? r : 0;
+  *ws_bytes = gemm_workspace_bytes(a);
+  if (!out) return 0;
+  IRX_CHECK(*up2_ok, "shape does not take the per-parity upsampler convs");
+  IRX_CHECK(x && w2, "null buffer");
+  IRX_CHECK(!*rows || parts, "this call emits GroupNorm partials: give the buffer");
+  IRX_CHECK(ws || !*ws_bytes, "split-K workspace missing");
+  const size_t per = (size_t)c * 4 * c * (dtype == F32 ? 4 : 2);   // one parity's [Cout][2][2][Cin]
+  for (int par = 0; par < 4; ++par) {
+    GemmArgs q = a;
+    q.g.pad_t = 1 - (par >> 1);
+    q.g.pad_l = 1 - (par & 1);
+    q.B = (const char*)w2 + par * per;
+    q.up2_p = par;
+    q.gn_part = *rows ? parts : nullptr;
+    q.splitk_ws = ws;
+    q.splitk_ws_bytes = *ws_bytes;
+    gemm(q, S(s));
+  }
+  IRX_API_END
+}
+
+int irx_op_group_norm_parts(void* s, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hw,
+                            int groups, float eps, const float* gamma, const float* beta, int silu, void* out,
+                            const double* p0, int r0, const double* p1, int r1, void* ws) {
+  IRX_API_BEGIN
+  IRX_CHECK(x0 && gamma && beta && out && ws, "null buffer");
+  group_norm_parts(dtype, x0, x1, c0, c1, n, hw, groups, eps, gamma, beta, silu, out, p0, r0, p1, r1, ws, S(s));
+  IRX_API_END
+}
+
+int irx_op_group_norm_parts_ab(void* s, int c0, int n, int hw, int groups, float eps, const float* gamma,
+                               const float* beta, const double* p0, int r0, void* ab, void* mr) {
+  IRX_API_BEGIN
+  IRX_CHECK(gamma && beta && ab, "null buffer");
+  group_norm_parts_ab(c0, n, hw, groups, eps, gamma, beta, p0, r0, (float2*)ab, (float2*)mr, S(s));
+  IRX_API_END
+}
+
 int irx_op_geglu(void* s, int dtype, const void* proj, int M, int F, void* out) {
   IRX_API_BEGIN
   IRX_CHECK(proj && out, "null buffer");

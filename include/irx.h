@@ -386,6 +386,42 @@ int irx_op_gemm_ln_out(void* stream, int dtype, int M, int N, int K, const void*
    (parts, irx_op_gemm_ln_out; K = 320 T).  geglu != 0: B / u / v in the GEGLU64 row order, C gets N / 2 columns. */
 int irx_op_gemm_ln_fold(void* stream, int dtype, int M, int N, int K, const void* A, const void* B, const float* u,
                         const float* v, const void* rs, const void* parts, int T, int geglu, void* C);
+/* GroupNorm statistics from producer partials: the 16-bit UNet / VAE GroupNorms read (sum, sum of squares) blocks
+   written by the kernel that stored the tensor instead of making a statistics pass.  The three producers below run
+   the GEMM exactly as the models do (same arguments, same plan, split-K partials from `ws`) and write, next to the
+   output, parts[block][channel] = (sum, sum of squares) (two doubles) of the stored values over blocks of *rows
+   consecutive output rows of one image (row = pixel of the [n][ho][wo] output); the strip halo tiles' blocks are 8 x 32
+   pixel strips, and only an image's total is defined there.  *rows == 0: this call emits none and `parts` stays
+   untouched.  With out / C == NULL nothing is launched: the call only fills the out-parameters, *ws_bytes included
+   (the bytes `ws` must hold).
+   conv: the arguments of irx_op_conv2d; *splits = K splits of the large-tile path (0: not on it), *halo = the halo
+   main loop the plan launches (0: not a halo conv; 2 whole-row tiles, 5 strip tiles, 8 four 8x8 images per tile).
+   *rows == 64 with *splits > 2 is the split-K reduce kernel's emission; two splits reduce in the kernel. */
+int irx_op_conv2d_gn_parts(void* stream, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hin,
+                           int win, int hv, int wv, const void* weight, const float* bias, int cout, int kh, int kw,
+                           int stride, int pad_t, int pad_l, int ho, int wo, const float* rowadd, long rowadd_ld,
+                           const void* residual, void* out, int out_f32, int act, double* parts, void* ws, int* rows,
+                           int* splits, int* halo, size_t* ws_bytes);
+/* dense: C[M][N] = A[M][K] B[N][K]^T + bias + residual (all contiguous) over `imgs` images of M / imgs rows */
+int irx_op_gemm_gn_parts(void* stream, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,
+                         const void* residual, int imgs, void* C, double* parts, void* ws, int* rows, int* splits,
+                         size_t* ws_bytes);
+/* nearest-2x upsample + 3x3 conv as four per-parity 2x2 convs (IRX_LAYOUT_CONV_UP2 weights w2 [4][c][2][2][c]):
+   x [n][h][w][c] -> out [n][2h][2w][c].  Partial block (image * 4 + p) * (h w / *rows) + j holds rows j * *rows ...
+   of the low-resolution pixels of parity p = 2a + b, i.e. of out[image][a::2][b::2] flattened; parts has
+   4 n h w / *rows blocks.  *up2_ok = 0: the shape does not take this form (running it is an error). */
+int irx_op_upsample_conv_gn_parts(void* stream, int dtype, const void* x, int n, int h, int w, int c, const void* w2,
+                                  const float* bias, void* out, double* parts, void* ws, int* up2_ok, int* rows,
+                                  size_t* ws_bytes);
+/* the consumers: GroupNorm(+SiLU) of (x0 | x1) from the partials p0 / p1 of r0 / r1 rows per block (finalize + apply,
+   or the fused kernel of option gn_fa); ws: irx_op_group_norm_ws_bytes */
+int irx_op_group_norm_parts(void* stream, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hw,
+                            int groups, float eps, const float* gamma, const float* beta, int silu, void* out,
+                            const double* p0, int r0, const double* p1, int r1, void* ws);
+/* ... the finalize alone: ab[n][c0] = (gamma rstd, beta - mean gamma rstd), mr[n][groups] = (mean, rstd) (mr may be
+   NULL); both pairs of floats */
+int irx_op_group_norm_parts_ab(void* stream, int c0, int n, int hw, int groups, float eps, const float* gamma,
+                               const float* beta, const double* p0, int r0, void* ab, void* mr);
 
 #ifdef __cplusplus
 }

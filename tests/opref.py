@@ -105,6 +105,98 @@ def gn_conv3(x0, gamma, beta, eps, w_oihw, bias, groups=32, silu=True, x1=None, 
     return out
 
 
+# ------------------------------------------------------------------ GroupNorm producer partials and their consumers
+def _nan_parts(blocks, Cn, device):
+    return torch.full((max(1, blocks), Cn, 2), float("nan"), dtype=torch.float64, device=device)
+
+
+def conv2d_gn_parts(x0, w_oihw, bias, x1=None, rowadd=None, residual=None, out_f32=False, pad=1):
+    """The conv as a model runs it for a GroupNorm to follow (irx_op_conv2d_gn_parts; stride 1, same size) ->
+    (out, parts [M / R][Co][2] float64 or, when nothing is emitted, the NaN-filled buffer, info).  info = the plan's
+    answer: rows per partial R (0: none), K splits, halo main loop.  The buffer is NaN before the call."""
+    dt = x0.dtype
+    N, H, W, C0 = x0.shape
+    C1 = x1.shape[3] if x1 is not None else 0
+    Co, Ci, KH, KW = w_oihw.shape
+    assert Ci == C0 + C1
+    wk = w_oihw.permute(0, 2, 3, 1).contiguous().to(device=x0.device, dtype=dt)
+    b = bias.float().to(x0.device).contiguous() if bias is not None else None
+    out = torch.empty((N, H, W, Co), dtype=torch.float32 if out_f32 else dt, device=x0.device)
+    rows, splits, halo, wsb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+
+    def call(o, parts, ws):
+        L.call("irx_op_conv2d_gn_parts", S(), DT[dt], P(x0), P(x1), C0, C1, N, H, W, H, W, P(wk), P(b), Co, KH, KW, 1,
+               pad, pad, H, W, P(rowadd), rowadd.shape[1] if rowadd is not None else 0, P(residual), P(o),
+               int(out_f32), 0, P(parts), P(ws), C.byref(rows), C.byref(splits), C.byref(halo), C.byref(wsb))
+        return {"R": rows.value, "splits": splits.value, "halo": halo.value}
+
+    q = call(None, None, None)
+    parts = _nan_parts(N * H * W // (q["R"] or 64), Co, x0.device)
+    ws = torch.empty(max(16, wsb.value), dtype=torch.uint8, device=x0.device)
+    assert call(out, parts, ws) == q
+    return out, parts, q
+
+
+def gemm_gn_parts(A, Bw, bias, residual, imgs, out_f32=False):
+    """Model::linear's form with GroupNorm partials (irx_op_gemm_gn_parts) -> (C, parts, info) as conv2d_gn_parts."""
+    dt = A.dtype
+    M, K = A.shape
+    N = Bw.shape[0]
+    assert not out_f32     # (the models' linear takes out_f32, a GroupNorm never reads such an output)
+    out = torch.empty((M, N), dtype=dt, device=A.device)
+    rows, splits, wsb = C.c_int(), C.c_int(), C.c_size_t()
+
+    def call(o, parts, ws):
+        L.call("irx_op_gemm_gn_parts", S(), DT[dt], M, N, K, P(A), P(Bw), P(bias), P(residual), imgs, P(o), P(parts),
+               P(ws), C.byref(rows), C.byref(splits), C.byref(wsb))
+        return {"R": rows.value, "splits": splits.value, "halo": 0}
+
+    q = call(None, None, None)
+    parts = _nan_parts(M // (q["R"] or 64), N, A.device)
+    ws = torch.empty(max(16, wsb.value), dtype=torch.uint8, device=A.device)
+    assert call(out, parts, ws) == q
+    return out, parts, q
+
+
+def upsample_conv_gn_parts(x, w2, bias):
+    """x [n][h][w][c], w2 [4 c][2][2][c] (engine.conv_up2, device, x's dtype) -> (out [n][2h][2w][c], parts
+    [4 n h w / R][c][2], info) through irx_op_upsample_conv_gn_parts."""
+    n, h, w, c = x.shape
+    out = torch.empty((n, 2 * h, 2 * w, c), dtype=x.dtype, device=x.device)
+    ok, rows, wsb = C.c_int(), C.c_int(), C.c_size_t()
+
+    def call(o, parts, ws):
+        L.call("irx_op_upsample_conv_gn_parts", S(), DT[x.dtype], P(x), n, h, w, c, P(w2), P(bias), P(o), P(parts),
+               P(ws), C.byref(ok), C.byref(rows), C.byref(wsb))
+        return {"up2": ok.value, "R": rows.value}
+
+    q = call(None, None, None)
+    parts = _nan_parts(4 * n * h * w // (q["R"] or 64), c, x.device)
+    ws = torch.empty(max(16, wsb.value), dtype=torch.uint8, device=x.device)
+    assert call(out, parts, ws) == q
+    return out, parts, q
+
+
+def group_norm_parts(x0, p0, r0, gamma, beta, eps, groups=32, silu=False, x1=None, p1=None, r1=0):
+    """GroupNorm(+SiLU) of (x0 | x1) [N][HW][C] from the partials p0 / p1 (irx_op_group_norm_parts)."""
+    N, HW, C0 = x0.shape
+    C1 = x1.shape[2] if x1 is not None else 0
+    ws = torch.empty(L.load().irx_op_group_norm_ws_bytes(N, HW, groups), dtype=torch.uint8, device=x0.device)
+    out = torch.empty((N, HW, C0 + C1), dtype=x0.dtype, device=x0.device)
+    L.call("irx_op_group_norm_parts", S(), DT[x0.dtype], P(x0), P(x1), C0, C1, N, HW, groups, float(eps), P(gamma),
+           P(beta), int(silu), P(out), P(p0), r0, P(p1), r1, P(ws))
+    return out
+
+
+def group_norm_parts_ab(p0, r0, C0, N, HW, gamma, beta, eps, groups=32):
+    """-> (ab [N][C0][2], mr [N][groups][2]) fp32: scale / shift per channel and (mean, rstd) per group."""
+    ab = torch.full((N, C0, 2), float("nan"), dtype=torch.float32, device=p0.device)
+    mr = torch.full((N, groups, 2), float("nan"), dtype=torch.float32, device=p0.device)
+    L.call("irx_op_group_norm_parts_ab", S(), C0, N, HW, groups, float(eps), P(gamma), P(beta), P(p0), r0, P(ab),
+           P(mr))
+    return ab, mr
+
+
 def layer_norm(x, gamma, beta, eps):
     rows, Cc = x.shape
     out = torch.empty_like(x)
