@@ -127,6 +127,9 @@ _SIGS = {
     "irx_median_blur_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32]),
     "irx_resample_coeffs": (i32, [i32, i32, i32, vp, vp, i32, C.POINTER(i32)]),
     "irx_resample_u8": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
+    "irx_metrics_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "irx_metrics_pair_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "irx_resize_linear_u8": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
     "irx_op_conv2d": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32,
                             i32, i32, i32, vp, i64, vp, vp, i32, i32]),
     "irx_op_gemm": (i32, [vp, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, f32, i32, vp, i64, i32, i32, i64,

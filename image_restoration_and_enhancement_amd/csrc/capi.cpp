@@ -616,6 +616,31 @@ int irx_resample_u8(void* s, const uint8_t* src, int batch, int H, int W, int C,
   if (batch) resample_u8(src, batch, H, W, C, xbounds, xcoeffs, xk, ybounds, ycoeffs, yk, h, w, dst, S(s));
   IRX_API_END
 }
+// ------------------------------------------------------------------ evaluation metrics (metrics.hip)
+long irx_metrics_ws_bytes(int batch, int H, int W, int C) { return metrics_ws_bytes(batch, H, W, C); }
+int irx_metrics_pair_u8(void* s, const uint8_t* pred, const uint8_t* gt, int batch, int H, int W, int C,
+                        const float* srgb_lut, void* ws, long long* sse, double* ssim, double* delta_e) {
+  IRX_API_BEGIN
+  IRX_CHECK(pred && gt && sse && ssim, "null image or output pointer");
+  IRX_CHECK(batch > 0, "batch must be positive");
+  IRX_CHECK(C == 1 || C == 3, "1 or 3 channels");
+  IRX_CHECK(H >= 7 && W >= 7, "SSIM's 7x7 window: H, W >= 7");
+  IRX_CHECK(!delta_e || C == 3, "dE76 needs 3 channels");
+  IRX_CHECK(!delta_e || srgb_lut, "dE76 needs the sRGB table");
+  IRX_CHECK(ws, "null workspace");
+  IRX_CHECK(((uintptr_t)ws & 7) == 0, "workspace must be 8-byte aligned");
+  metrics_pair_u8(pred, gt, batch, H, W, C, srgb_lut, ws, sse, ssim, delta_e, S(s));
+  IRX_API_END
+}
+int irx_resize_linear_u8(void* s, const uint8_t* src, int batch, int H, int W, int C, const int* xtab,
+                         const int* ytab, int h, int w, uint8_t* dst) {
+  IRX_API_BEGIN
+  IRX_CHECK(src && dst && src != dst && xtab && ytab, "null image or table pointer");
+  IRX_CHECK(batch > 0 && H > 0 && W > 0 && h > 0 && w > 0, "batch and sizes must be positive");
+  IRX_CHECK(C == 1 || C == 3, "1 or 3 channels");
+  resize_linear_u8(src, batch, H, W, C, xtab, ytab, h, w, dst, S(s));
+  IRX_API_END
+}
 // ------------------------------------------------------------------ single ops
 int irx_op_conv2d(void* s, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hin, int win, int hv,
                   int wv, const void* weight, const float* bias, int cout, int kh, int kw, int stride, int pad_t,

@@ -361,5 +361,11 @@ void median5_u8(const uint8_t* src, uint8_t* dst, int N, int H, int W, int C, hi
 // ------------------------------------------------------------ PIL resize (resample.hip)
 void resample_u8(const uint8_t* src, int B, int H, int W, int C, const int* xb, const int* xc, int xk, const int* yb,
                  const int* yc, int yk, int h, int w, uint8_t* dst, hipStream_t s);
+// ------------------------------------------------------------ evaluation metrics (metrics.hip)
+long metrics_ws_bytes(int B, int H, int W, int C);      // 0: a shape metrics_pair_u8 refuses
+void metrics_pair_u8(const uint8_t* pred, const uint8_t* gt, int B, int H, int W, int C, const float* lut, void* ws,
+                     long long* sse, double* ssim, double* de, hipStream_t s);
+void resize_linear_u8(const uint8_t* src, int B, int H, int W, int C, const int* xt, const int* yt, int h, int w,
+                      uint8_t* dst, hipStream_t s);
 
 }  // namespace irx

@@ -20,6 +20,10 @@ PSNR / SSIM / rgb2lab are pinned against scikit-image 0.18.3 outputs committed u
 restatements without an oracle in this image (cv2 is absent): parity unpinned.  LPIPS and FID need
 network-downloaded networks and stay unavailable, exactly as the reference behaves without
 `lpips`/torchvision (`src/metrics.py:24-37`).
+
+With `device="cuda"` the calculator and `evaluate_task` score on the GPU (`metrics_gpu`, csrc/metrics.hip): PSNR
+bit-equal to the functions below, SSIM and dE76 to 1e-9.  The module-level functions and
+`device="cpu"` are the numpy code and the oracle of that path.
 """
 from __future__ import annotations
 
@@ -48,26 +52,28 @@ def load_image(path: Path) -> np.ndarray:
         raise ValueError(f"Could not load image: {path}")
 
 
+def linear_axis(n_out: int, n_in: int):
+    """One axis of cv2's INTER_LINEAR for uint8: (i0, i1, w0, w1) per output index, the two source indices and
+    their 11-bit weights (w0 + w1 = 2048).  Shared by `resize_linear` and the GPU tables (`metrics_gpu`)."""
+    scale = n_in / n_out
+    f = (np.arange(n_out) + 0.5) * scale - 0.5
+    i0 = np.floor(f).astype(np.int64)
+    f = f - i0
+    lo = i0 < 0
+    f[lo], i0[lo] = 0.0, 0
+    hi = i0 >= n_in - 1
+    f[hi], i0[hi] = 0.0, n_in - 1
+    w1 = np.rint(f * 2048).astype(np.int64)
+    return i0, np.minimum(i0 + 1, n_in - 1), 2048 - w1, w1
+
+
 def resize_linear(img: np.ndarray, width: int, height: int) -> np.ndarray:
     """cv2.resize(img, (width, height)) with INTER_LINEAR for uint8 images."""
     H, W = img.shape[:2]
     if (H, W) == (height, width):
         return img.copy()
-
-    def axis(n_out, n_in):
-        scale = n_in / n_out
-        f = (np.arange(n_out) + 0.5) * scale - 0.5
-        i0 = np.floor(f).astype(np.int64)
-        f = f - i0
-        lo = i0 < 0
-        f[lo], i0[lo] = 0.0, 0
-        hi = i0 >= n_in - 1
-        f[hi], i0[hi] = 0.0, n_in - 1
-        w1 = np.rint(f * 2048).astype(np.int64)
-        return i0, np.minimum(i0 + 1, n_in - 1), 2048 - w1, w1
-
-    y0, y1, wy0, wy1 = axis(height, H)
-    x0, x1, wx0, wx1 = axis(width, W)
+    y0, y1, wy0, wy1 = linear_axis(height, H)
+    x0, x1, wx0, wx1 = linear_axis(width, W)
     a = img.astype(np.int64)
     if a.ndim == 2:
         a = a[..., None]
@@ -115,12 +121,22 @@ def ssim(gt: np.ndarray, pred: np.ndarray, data_range: float = 255.0) -> float:
     return float(np.mean([_ssim_2d(gt[..., c], pred[..., c], data_range) for c in range(gt.shape[2])]))
 
 
-def rgb2lab(rgb: np.ndarray) -> np.ndarray:
-    """skimage.color.rgb2lab for float RGB in [0, 1] (D65, 2-degree observer)."""
+def srgb_linear(rgb: np.ndarray) -> np.ndarray:
+    """The sRGB linearisation in front of skimage's rgb2xyz, in the dtype of `rgb` (float32 for the dE path)."""
     arr = np.array(rgb, copy=True)
     mask = arr > 0.04045
     arr[mask] = np.power((arr[mask] + 0.055) / 1.055, 2.4)
     arr[~mask] /= 12.92
+    return arr
+
+
+def rgb2lab(rgb: np.ndarray) -> np.ndarray:
+    """skimage.color.rgb2lab for float RGB in [0, 1] (D65, 2-degree observer)."""
+    return lab_from_linear(srgb_linear(rgb))
+
+
+def lab_from_linear(arr: np.ndarray) -> np.ndarray:
+    """rgb2lab after the linearisation (fp64 from here on): XYZ, white point, cbrt / linear branch, Lab."""
     xyz = arr @ _XYZ_FROM_RGB.T
     xyz = xyz / _WHITE_D65
     mask = xyz > 0.008856
@@ -130,28 +146,94 @@ def rgb2lab(rgb: np.ndarray) -> np.ndarray:
     return np.stack([116.0 * y - 16.0, 500.0 * (x - y), 200.0 * (y - z)], axis=-1)
 
 
+def _to_host(img) -> np.ndarray:
+    """A numpy image from a numpy image or a (device) tensor."""
+    return img if isinstance(img, np.ndarray) else img.detach().cpu().numpy()
+
+
 class MetricsCalculator:
-    """Per-image metrics (reference `src/metrics.py:57-209`).  LPIPS/FID: unavailable offline."""
+    """Per-image metrics (reference `src/metrics.py:57-209`).  LPIPS/FID: unavailable offline.
+
+    `device="cpu"` (the default) is the numpy code above.  A `cuda*` string or torch.device scores on the GPU
+    (`metrics_gpu`, csrc/metrics.hip) when one is visible, `libirx.so` loads and the pair's shape is inside the
+    kernel's range (H, W >= 7, 1 or 3 channels); any other pair takes the numpy code.  Every method accepts numpy
+    images or uint8 device tensors ([H, W] or [H, W, C]), so `restore_batch` outputs are scored without a download."""
 
     def __init__(self, use_lpips: bool = True, use_fid: bool = True, device: str = "cpu"):
         self.use_lpips = use_lpips and LPIPS_AVAILABLE
         self.use_fid = use_fid and FID_AVAILABLE
         self.device = device
+        self._gpu = False       # metrics_gpu, None (host), or False: not decided yet
+
+    def _gpu_module(self):
+        """`metrics_gpu` when `device` names a GPU, one is visible and the native library loads; else None."""
+        if self._gpu is False:
+            self._gpu = None
+            if str(self.device).startswith("cuda"):
+                try:
+                    import torch
+                    if torch.cuda.is_available():
+                        from . import _lib, metrics_gpu
+                        _lib.load()
+                        self._gpu = metrics_gpu
+                except Exception:   # no torch, no library: the host code serves
+                    self._gpu = None
+        return self._gpu
+
+    def _device_pair(self, pred, gt, channels=(1, 3)):
+        """(pred, gt) as uint8 device tensors of gt's shape (pred resized on the GPU if its size differs), or None
+        when this pair takes the host code.  Two numpy images of one shape go up in one copy."""
+        G = self._gpu_module()
+        ps, gs = tuple(pred.shape), tuple(gt.shape)
+        if G is None or len(ps) != len(gs) or len(gs) not in (2, 3) or ps[2:] != gs[2:] or not G.supported(gs):
+            return None
+        if (gs[2] if len(gs) == 3 else 1) not in channels or min(ps[:2]) < 1:
+            return None
+        if any(str(x.dtype).rsplit(".", 1)[-1] != "uint8" for x in (pred, gt)):     # numpy or torch dtype
+            return None
+        if ps == gs and isinstance(pred, np.ndarray) and isinstance(gt, np.ndarray):
+            both = G.to_device(np.stack([pred, gt]), self.device)
+            return both[0], both[1]
+        p, g = G.to_device(pred, self.device), G.to_device(gt, self.device)
+        if ps != gs:
+            p = G.resize_linear_u8(p, gs[1], gs[0])
+        return p, g
+
+    def _device_stats(self, pred, gt):
+        """(device float64 [2] = (squared error, SSIM), values per image) without waiting for the device, or None
+        when this pair takes the host code.  The squared error is an integer below 2^53: exact as a double."""
+        pair = self._device_pair(pred, gt)
+        if pair is None:
+            return None
+        sse, ssim_, _ = self._gpu.pair_stats(pair[0], pair[1])
+        return self._gpu.torch.cat([sse.to(ssim_.dtype), ssim_]), pair[1].numel()
 
     @staticmethod
     def _match(pred: np.ndarray, gt: np.ndarray) -> np.ndarray:
         return pred if pred.shape == gt.shape else resize_linear(pred, gt.shape[1], gt.shape[0])
 
     def calculate_psnr(self, pred: np.ndarray, gt: np.ndarray) -> float:
+        pair = self._device_pair(pred, gt)
+        if pair is not None:
+            return self._gpu.psnr_from_sse(self._gpu.pair_stats(*pair)[0][0].item(), pair[1].numel())
+        pred, gt = _to_host(pred), _to_host(gt)
         return psnr(gt, self._match(pred, gt), data_range=255.0)
 
     def calculate_ssim(self, pred: np.ndarray, gt: np.ndarray) -> float:
+        pair = self._device_pair(pred, gt)
+        if pair is not None:
+            return float(self._gpu.pair_stats(*pair)[1][0].item())
+        pred, gt = _to_host(pred), _to_host(gt)
         return ssim(gt, self._match(pred, gt), data_range=255.0)
 
     def calculate_lpips(self, pred: np.ndarray, gt: np.ndarray):
         return None
 
     def calculate_delta_e(self, pred: np.ndarray, gt: np.ndarray, use_delta_e2000: bool = False) -> float:
+        pair = self._device_pair(pred, gt, channels=(3,))
+        if pair is not None:
+            return float(self._gpu.pair_stats(*pair, delta_e=True)[2][0].item())
+        pred, gt = _to_host(pred), _to_host(gt)
         pred = self._match(pred, gt)
         pl = rgb2lab(pred.astype(np.float32) / 255.0)
         gl = rgb2lab(gt.astype(np.float32) / 255.0)
@@ -161,7 +243,12 @@ class MetricsCalculator:
         return None
 
     def calculate_all(self, pred: np.ndarray, gt: np.ndarray) -> dict:
-        out = {"psnr": self.calculate_psnr(pred, gt), "ssim": self.calculate_ssim(pred, gt)}
+        dev = self._device_stats(pred, gt)      # one upload, the resize if the shapes differ, one pair_stats call
+        if dev is not None:
+            v = dev[0].cpu().numpy()
+            out = {"psnr": self._gpu.psnr_from_sse(int(v[0]), dev[1]), "ssim": float(v[1])}
+        else:
+            out = {"psnr": self.calculate_psnr(pred, gt), "ssim": self.calculate_ssim(pred, gt)}
         if self.use_lpips:
             out["lpips"] = self.calculate_lpips(pred, gt)
         return out
@@ -173,7 +260,8 @@ _EXTS = {".jpg", ".jpeg", ".png"}
 def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_lpips: bool = True,
                   use_fid: bool = True, device: str = "cpu") -> dict:
     """Match predictions to ground truth by file name (any of .jpg/.jpeg/.png) and aggregate
-    mean/std/min/max/median per metric (reference `src/metrics.py:238-348`)."""
+    mean/std/min/max/median per metric (reference `src/metrics.py:238-348`).  With a `cuda*` device the pairs are
+    scored on the GPU as they are loaded and read back together, one synchronisation per task."""
     pred_dir, gt_dir = Path(pred_dir), Path(gt_dir)
     calc = MetricsCalculator(use_lpips=use_lpips, use_fid=use_fid, device=device)
     pred_files = sorted(f for f in pred_dir.iterdir() if f.suffix.lower() in _EXTS)
@@ -197,15 +285,33 @@ def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_
     if use_lpips:
         all_metrics["lpips"] = []
     print(f"Evaluating {task_name}: {len(pairs)} image pairs...")
+    pending = []    # GPU path: (slot in the psnr / ssim lists, device (squared error, SSIM), values per image)
     for i, (pp, gp) in enumerate(pairs):
         try:
-            for k, v in calc.calculate_all(load_image(pp), load_image(gp)).items():
-                if v is not None:
-                    all_metrics[k].append(v)
+            pred, gt = load_image(pp), load_image(gp)
+            dev = calc._device_stats(pred, gt)
+            if dev is not None:                 # enqueued; read back after the loop, all pairs in one download
+                pending.append((len(all_metrics["psnr"]),) + dev)
+                all_metrics["psnr"].append(None)
+                all_metrics["ssim"].append(None)
+                if calc.use_lpips:
+                    v = calc.calculate_lpips(pred, gt)
+                    if v is not None:
+                        all_metrics["lpips"].append(v)
+            else:
+                for k, v in calc.calculate_all(pred, gt).items():
+                    if v is not None:
+                        all_metrics[k].append(v)
             if (i + 1) % 10 == 0:
                 print(f"  Processed {i + 1}/{len(pairs)}")
         except Exception as e:  # the reference skips unreadable pairs
             print(f"Error processing {pp.name}: {e}")
+    if pending:
+        G = calc._gpu_module()
+        vals = G.torch.stack([t for _, t, _ in pending]).cpu().numpy()     # the task's one synchronisation
+        for (slot, _, n), v in zip(pending, vals):
+            all_metrics["psnr"][slot] = G.psnr_from_sse(int(v[0]), n)
+            all_metrics["ssim"][slot] = float(v[1])
     res = {"task": task_name, "num_samples": len(pairs), "metrics": {}}
     for k, vals in all_metrics.items():
         if vals:

@@ -292,6 +292,31 @@ int irx_resample_u8(void* stream, const uint8_t* src, int batch, int H, int W, i
                     const int* xcoeffs, int xk, const int* ybounds, const int* ycoeffs, int yk, int h, int w,
                     uint8_t* dst);
 
+/* ---- evaluation metrics on uint8 pairs (src/metrics.py; `evaluate_task`, scripts/evaluate_model.py) ----
+ * pred / gt [batch][H][W][C] in device memory, C = 1 or 3, H, W >= 7.  Per image:
+ *   sse[b]     = sum (gt - pred)^2 over pixels and channels, exact: skimage's peak_signal_noise_ratio is
+ *                10 log10(255^2 / (sse / (H W C))) (calculate_psnr, src/metrics.py:82-87);
+ *   ssim[b]    = skimage structural_similarity(gt, pred, data_range=255, channel_axis=2) with its defaults (7x7
+ *                uniform window, sample covariance, K1 0.01, K2 0.03, crop 3): calculate_ssim, src/metrics.py:89-95.
+ *                Window sums are exact integers, S and its sum fp64;
+ *   delta_e[b] = mean dE76 of skimage rgb2lab (calculate_delta_e, src/metrics.py:113-148), C = 3 only, when delta_e
+ *                is not NULL; srgb_lut = device float[256], the float32 sRGB linearisation of v / 255 for every byte
+ *                value (what rgb2lab computes in float32); the rest is fp64.
+ * The fp64 sums are added in a fixed order (block partials in ws, then a fixed tree; no atomics): bit-identical from
+ * run to run, for every position in the batch and every batch size.  Two launches, no allocation, no synchronisation.
+ * ws: irx_metrics_ws_bytes(batch, H, W, C) bytes of device memory, 8-byte aligned (0 is returned for arguments
+ * irx_metrics_pair_u8 would refuse).  A refused argument (null pointer, batch <= 0, C not 1 or 3, H or W < 7, delta_e
+ * with C = 1, null ws) is a status and launches nothing. */
+long irx_metrics_ws_bytes(int batch, int H, int W, int C);
+int irx_metrics_pair_u8(void* stream, const uint8_t* pred, const uint8_t* gt, int batch, int H, int W, int C,
+                        const float* srgb_lut, void* ws, long long* sse, double* ssim, double* delta_e);
+/* cv2.resize(img, (w, h)) with INTER_LINEAR for uint8, the shape match in front of every metric
+ * (src/metrics.py:84-86): [batch][H][W][C] -> [batch][h][w][C], C = 1 or 3, src != dst.  xtab int[w][3], ytab
+ * int[h][3] (device) = (i0, i1, w1) per output index: the two source indices and the 11-bit weight of the second
+ * (w0 = 2048 - w1); out = clip8((sum + 2^21) >> 22).  Integer, exact. */
+int irx_resize_linear_u8(void* stream, const uint8_t* src, int batch, int H, int W, int C, const int* xtab,
+                         const int* ytab, int h, int w, uint8_t* dst);
+
 /* ---- multi-GPU: RCCL over xGMI (SURVEY.md §8b `irx_weights_bcast(handle, rcclComm)`, §8e) ----
    The reference has no multi-device path (src/inference.py:52-57 picks one device; it stands in for
    `pipe.to("cuda")` at src/inference.py:175-176 on every rank but the first).  One process per GPU: rank 0
