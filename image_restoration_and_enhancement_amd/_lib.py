@@ -14,6 +14,7 @@ LIB_PATH = Path(os.environ.get("IRX_LIB", _PKG / "libirx.so"))
 
 IRX_F32, IRX_BF16, IRX_F16 = 0, 1, 2
 IRX_MODEL_UNET, IRX_MODEL_VAE, IRX_MODEL_CLIP = 0, 1, 2
+IRX_MODEL_LPIPS = 3       # LPIPS(alex), the reference's src/metrics.py:97-111
 IRX_LAYOUT_VEC, IRX_LAYOUT_MAT, IRX_LAYOUT_CONV, IRX_LAYOUT_EMB = 0, 1, 2, 3
 IRX_LAYOUT_MAT_GEGLU64, IRX_LAYOUT_VEC_GEGLU64 = 4, 5
 IRX_LAYOUT_VEC_LN_U, IRX_LAYOUT_VEC_LN_V = 6, 7
@@ -130,6 +131,11 @@ _SIGS = {
     "irx_metrics_ws_bytes": (i64, [i32, i32, i32, i32]),
     "irx_metrics_pair_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irx_resize_linear_u8": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
+    # LPIPS(alex): MetricsCalculator.calculate_lpips, src/metrics.py:97-111
+    "irx_lpips_workspace_bytes": (i32, [vp, i32, i32, i32, C.POINTER(sz)]),
+    "irx_lpips_u8": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz]),
+    "irx_op_lpips_input": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+    "irx_op_lpips_relu_pool": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "irx_op_conv2d": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32,
                             i32, i32, i32, vp, i64, vp, vp, i32, i32]),
     "irx_op_gemm": (i32, [vp, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, f32, i32, vp, i64, i32, i32, i64,

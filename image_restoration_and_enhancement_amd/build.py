@@ -32,6 +32,8 @@ PER_FILE = {"elementwise.hip": ["-ffp-contract=off"],
             "degrade_jpeg.hip": ["-ffp-contract=off"],
             # the fp64 SSIM / Lab formulas as written, operation for operation
             "metrics.hip": ["-ffp-contract=off"],
+            # the LPIPS head as lpips_host.py writes it: divisions, squares and sums as separate operations
+            "lpips.hip": ["-ffp-contract=off"],
             # Pillow's coefficient doubles: libm's sin, IEEE divisions, no FMA (csrc/resample_coeffs.cpp)
             "resample_coeffs.cpp": ["-ffp-contract=off", "-fno-fast-math"]}
 

@@ -229,6 +229,7 @@ int irx_model_create(int kind, const irx_model_config* cfg, int dtype, irx_model
     if (kind == IRX_MODEL_UNET) h->m.reset(new Unet(*cfg, dtype));
     else if (kind == IRX_MODEL_VAE) h->m.reset(new Vae(*cfg, dtype));
     else if (kind == IRX_MODEL_CLIP) h->m.reset(new Clip(*cfg, dtype));
+    else if (kind == IRX_MODEL_LPIPS) h->m.reset(new LpipsAlex(*cfg, dtype));
     else throw Error("unknown model kind");
   } catch (...) {
     delete h;
@@ -639,6 +640,39 @@ int irx_resize_linear_u8(void* s, const uint8_t* src, int batch, int H, int W, i
   IRX_CHECK(batch > 0 && H > 0 && W > 0 && h > 0 && w > 0, "batch and sizes must be positive");
   IRX_CHECK(C == 1 || C == 3, "1 or 3 channels");
   resize_linear_u8(src, batch, H, W, C, xtab, ytab, h, w, dst, S(s));
+  IRX_API_END
+}
+// ------------------------------------------------------------------ LPIPS(alex) (lpips_model.cpp, lpips.hip;
+// MetricsCalculator.calculate_lpips, src/metrics.py:97-111)
+int irx_lpips_workspace_bytes(const irx_model* m, int B, int H, int W, size_t* bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(bytes, "null argument");
+  *bytes = const_cast<LpipsAlex*>(as<LpipsAlex>(m, IRX_MODEL_LPIPS))->workspace_bytes(B, H, W);
+  IRX_API_END
+}
+int irx_lpips_u8(irx_model* m, void* s, const uint8_t* pred, const uint8_t* gt, int B, int H, int W,
+                 const float* in_lut, double* total, double* layers, void* ws, size_t ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(pred && gt && in_lut && total && ws, "null image, table, output or workspace pointer");
+  IRX_CHECK(B > 0, "batch must be positive");
+  IRX_CHECK(H >= LpipsAlex::kMinSide && W >= LpipsAlex::kMinSide, "LPIPS(alex): H, W >= 31");
+  as<LpipsAlex>(m, IRX_MODEL_LPIPS)->score(S(s), pred, gt, B, H, W, in_lut, total, layers, (char*)ws, ws_bytes);
+  IRX_API_END
+}
+int irx_op_lpips_input(void* s, const uint8_t* pred, const uint8_t* gt, int B, int H, int W, const float* in_lut,
+                       float* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(pred && gt && in_lut && out, "null buffer");
+  IRX_CHECK(B > 0 && H > 0 && W > 0, "batch and sizes must be positive");
+  IRX_CHECK(((uintptr_t)out % 16) == 0, "output must be 16-byte aligned");
+  lpips_input(pred, gt, B, H, W, in_lut, out, S(s));
+  IRX_API_END
+}
+int irx_op_lpips_relu_pool(void* s, const float* x, int n, int H, int W, int C, int win, int stride, float* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(x && out && x != out, "null buffer");
+  IRX_CHECK(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0, "buffers must be 16-byte aligned");
+  lpips_relu_pool(x, n, H, W, C, win, stride, out, S(s));
   IRX_API_END
 }
 // ------------------------------------------------------------------ single ops

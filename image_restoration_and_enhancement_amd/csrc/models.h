@@ -1,4 +1,4 @@
-// irx — native model graphs (UNet2DConditionModel, AutoencoderKL, CLIPTextModel) over the irx kernels.
+// irx — native model graphs (UNet2DConditionModel, AutoencoderKL, CLIPTextModel, LPIPS AlexNet) over the irx kernels.
 #pragma once
 #include <map>
 #include <memory>
@@ -235,6 +235,24 @@ class Clip : public Model {
   void run(Ctx& c, const int* ids, int B, int L, void* out);
   P tok, pos, fw, fb;
   std::vector<Layer> layers_;
+};
+
+// LPIPS(alex) v0.1, eval mode, spatial = false (lpips_host.py; the reference's src/metrics.py:97-111): the AlexNet
+// trunk on gemm()'s exact-f32 path over NHWC fp32 activations, pred and gt as one batch of 2B images, and the per-tap
+// heads of lpips.hip.  fp32 only; the config is not read.
+class LpipsAlex : public Model {
+ public:
+  LpipsAlex(const irx_model_config& cfg, int dtype);
+  static constexpr int kMinSide = 31;   // below it the second pool has no window left
+  size_t workspace_bytes(int B, int H, int W);
+  // pred / gt uint8 [B][H][W][3]; lut float[256][3] (lpips_host.input_table); total [B]; layers [B][5] or null
+  void score(hipStream_t s, const uint8_t* pred, const uint8_t* gt, int B, int H, int W, const float* lut,
+             double* total, double* layers, char* ws, size_t cap);
+
+ private:
+  void run(Ctx& c, const uint8_t* pred, const uint8_t* gt, int B, int H, int W, const float* lut, double* total,
+           double* layers);
+  P cw_[5], cb_[5], lw_[5];
 };
 
 }  // namespace irx

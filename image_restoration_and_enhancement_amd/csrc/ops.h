@@ -367,5 +367,16 @@ void metrics_pair_u8(const uint8_t* pred, const uint8_t* gt, int B, int H, int W
                      long long* sse, double* ssim, double* de, hipStream_t s);
 void resize_linear_u8(const uint8_t* src, int B, int H, int W, int C, const int* xt, const int* yt, int h, int w,
                       uint8_t* dst, hipStream_t s);
+// ------------------------------------------------------------ LPIPS (lpips.hip; the trunk: LpipsAlex, models.h)
+// uint8 [B][H][W][3] of pred and of gt -> fp32 [2B][H][W][4] (pred first, channel 3 zero) through lut float[256][3]
+void lpips_input(const uint8_t* pred, const uint8_t* gt, int B, int H, int W, const float* lut, float* out,
+                 hipStream_t s);
+// ReLU, then max over win x win at `stride`, no padding: (3, 2) or (1, 1); fp32 NHWC, C % 4 == 0
+void lpips_relu_pool(const float* x, int N, int H, int W, int C, int win, int stride, float* y, hipStream_t s);
+int lpips_head_blocks(int hw);   // partials per image of a tap with hw pixels
+// one tap: f fp32 [2B][hw][C] pre-ReLU (pred first), w [C]; part [B][lpips_head_blocks(hw)], lay [B][5] (workspace);
+// writes lay[b][tap] (and layers[b][tap] if not null); tap 4 also writes total[b] = the five in index order
+void lpips_head(const float* f, int B, int hw, int C, const float* w, int tap, double* part, double* lay,
+                double* layers, double* total, hipStream_t s);
 
 }  // namespace irx

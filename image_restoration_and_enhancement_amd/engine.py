@@ -34,6 +34,8 @@ def dtype_code(dtype) -> int:
 
 def model_config(kind: int, cfg) -> L.ModelConfig:
     c = L.ModelConfig()
+    if kind == L.IRX_MODEL_LPIPS:       # fixed architecture: the native model does not read the config
+        return c
     if kind == L.IRX_MODEL_UNET:
         assert isinstance(cfg, UNetConfig)
         c.in_channels, c.out_channels = cfg.in_channels, cfg.out_channels

@@ -17,9 +17,14 @@ arithmetic restated:
 
 PSNR / SSIM / rgb2lab are pinned against scikit-image 0.18.3 outputs committed under
 `tests/golden/metrics.json` (tests/test_metrics.py).  The INTER_LINEAR resize and JPEG decode are
-restatements without an oracle in this image (cv2 is absent): parity unpinned.  LPIPS and FID need
-network-downloaded networks and stay unavailable, exactly as the reference behaves without
-`lpips`/torchvision (`src/metrics.py:24-37`).
+restatements without an oracle in this image (cv2 is absent): parity unpinned.  FID needs a network-downloaded
+InceptionV3 and stays unavailable, exactly as the reference behaves without torchvision (`src/metrics.py:24-37`).
+
+LPIPS(alex) (`src/metrics.py:97-111`) is computed when the user points at the two weight files it needs —
+`lpips_weights=` or the environment variable `IRX_LPIPS_WEIGHTS` (a directory or a file, `lpips_host.load_weights`);
+the code is `lpips_host` (plain torch) on the host and `lpips_gpu` (csrc/lpips.hip) with `device="cuda"`.  With
+nothing configured the metric is off as before: `use_lpips` is False, `calculate_lpips` returns None, and the module
+constant `LPIPS_AVAILABLE` (the `lpips` package itself) stays False.  A path that is set but cannot be read is an error.
 
 With `device="cuda"` the calculator and `evaluate_task` score on the GPU (`metrics_gpu`, csrc/metrics.hip): PSNR
 bit-equal to the functions below, SSIM and dE76 to 1e-9.  The module-level functions and
@@ -27,6 +32,7 @@ bit-equal to the functions below, SSIM and dE76 to 1e-9.  The m
 """
 from __future__ import annotations
 
+import os
 from pathlib import Path
 
 import numpy as np
@@ -35,6 +41,7 @@ from scipy.ndimage import uniform_filter
 
 LPIPS_AVAILABLE = False
 FID_AVAILABLE = False
+LPIPS_WEIGHTS_ENV = "IRX_LPIPS_WEIGHTS"
 
 # skimage.color: sRGB (D65) -> XYZ and the D65 / 2-degree white point
 _XYZ_FROM_RGB = np.array([[0.412453, 0.357580, 0.180423],
@@ -151,19 +158,33 @@ def _to_host(img) -> np.ndarray:
     return img if isinstance(img, np.ndarray) else img.detach().cpu().numpy()
 
 
+def resolve_lpips_weights(lpips_weights=None):
+    """The LPIPS(alex) weights as a checked dict, or None when nothing is configured: `lpips_weights` (a dict of
+    tensors, or a directory / file for `lpips_host.load_weights`), else the path in `IRX_LPIPS_WEIGHTS`.  A source
+    that is given but cannot be read raises."""
+    src = lpips_weights if lpips_weights is not None else (os.environ.get(LPIPS_WEIGHTS_ENV) or None)
+    if src is None:
+        return None
+    from . import lpips_host
+    return lpips_host.check_weights(src) if isinstance(src, dict) else lpips_host.load_weights(src)
+
+
 class MetricsCalculator:
-    """Per-image metrics (reference `src/metrics.py:57-209`).  LPIPS/FID: unavailable offline.
+    """Per-image metrics (reference `src/metrics.py:57-209`).  FID: unavailable offline.  LPIPS(alex): on when
+    weights are configured (`lpips_weights` or `IRX_LPIPS_WEIGHTS`), see the module docstring.
 
     `device="cpu"` (the default) is the numpy code above.  A `cuda*` string or torch.device scores on the GPU
     (`metrics_gpu`, csrc/metrics.hip) when one is visible, `libirx.so` loads and the pair's shape is inside the
     kernel's range (H, W >= 7, 1 or 3 channels); any other pair takes the numpy code.  Every method accepts numpy
     images or uint8 device tensors ([H, W] or [H, W, C]), so `restore_batch` outputs are scored without a download."""
 
-    def __init__(self, use_lpips: bool = True, use_fid: bool = True, device: str = "cpu"):
-        self.use_lpips = use_lpips and LPIPS_AVAILABLE
+    def __init__(self, use_lpips: bool = True, use_fid: bool = True, device: str = "cpu", lpips_weights=None):
+        self._lpips_w = resolve_lpips_weights(lpips_weights) if use_lpips else None
+        self.use_lpips = self._lpips_w is not None
         self.use_fid = use_fid and FID_AVAILABLE
         self.device = device
         self._gpu = False       # metrics_gpu, None (host), or False: not decided yet
+        self._lpips_net = None  # lpips_gpu.LpipsAlex, made at the first GPU score
 
     def _gpu_module(self):
         """`metrics_gpu` when `device` names a GPU, one is visible and the native library loads; else None."""
@@ -199,14 +220,31 @@ class MetricsCalculator:
             p = G.resize_linear_u8(p, gs[1], gs[0])
         return p, g
 
-    def _device_stats(self, pred, gt):
+    def _device_stats(self, pred, gt, pair=None):
         """(device float64 [2] = (squared error, SSIM), values per image) without waiting for the device, or None
         when this pair takes the host code.  The squared error is an integer below 2^53: exact as a double."""
-        pair = self._device_pair(pred, gt)
+        pair = self._device_pair(pred, gt) if pair is None else pair
         if pair is None:
             return None
         sse, ssim_, _ = self._gpu.pair_stats(pair[0], pair[1])
         return self._gpu.torch.cat([sse.to(ssim_.dtype), ssim_]), pair[1].numel()
+
+    def _lpips_pair(self, pair):
+        """Device float64 [1]: LPIPS of a `_device_pair` result, enqueued without waiting; None when the pair is
+        outside the GPU model's range (not RGB, a side below 31) and the host code decides."""
+        if pair is None:
+            return None
+        from . import lpips_gpu
+        if not lpips_gpu.supported(pair[1].shape):
+            return None
+        if self._lpips_net is None:
+            self._lpips_net = lpips_gpu.LpipsAlex(self._lpips_w, self.device)
+        return self._lpips_net.score(pair[0], pair[1])
+
+    def _lpips_host(self, pred, gt) -> float:
+        from . import lpips_host
+        pred, gt = _to_host(pred), _to_host(gt)
+        return float(lpips_host.lpips_alex(self._match(pred, gt), gt, self._lpips_w)[0][0])
 
     @staticmethod
     def _match(pred: np.ndarray, gt: np.ndarray) -> np.ndarray:
@@ -227,7 +265,11 @@ class MetricsCalculator:
         return ssim(gt, self._match(pred, gt), data_range=255.0)
 
     def calculate_lpips(self, pred: np.ndarray, gt: np.ndarray):
-        return None
+        """LPIPS(alex) of one pair (reference `src/metrics.py:97-111`), or None when no weights are configured."""
+        if not self.use_lpips:
+            return None
+        dev = self._lpips_pair(self._device_pair(pred, gt, channels=(3,)))
+        return float(dev[0].item()) if dev is not None else self._lpips_host(pred, gt)
 
     def calculate_delta_e(self, pred: np.ndarray, gt: np.ndarray, use_delta_e2000: bool = False) -> float:
         pair = self._device_pair(pred, gt, channels=(3,))
@@ -243,12 +285,16 @@ class MetricsCalculator:
         return None
 
     def calculate_all(self, pred: np.ndarray, gt: np.ndarray) -> dict:
-        dev = self._device_stats(pred, gt)      # one upload, the resize if the shapes differ, one pair_stats call
-        if dev is not None:
-            v = dev[0].cpu().numpy()
+        pair = self._device_pair(pred, gt)      # one upload, the resize if the shapes differ
+        if pair is not None:                    # one pair_stats call, LPIPS behind it, one download
+            dev = self._device_stats(pred, gt, pair)
+            lp = self._lpips_pair(pair) if self.use_lpips else None
+            v = (dev[0] if lp is None else self._gpu.torch.cat([dev[0], lp])).cpu().numpy()
             out = {"psnr": self._gpu.psnr_from_sse(int(v[0]), dev[1]), "ssim": float(v[1])}
-        else:
-            out = {"psnr": self.calculate_psnr(pred, gt), "ssim": self.calculate_ssim(pred, gt)}
+            if self.use_lpips:
+                out["lpips"] = float(v[2]) if lp is not None else self._lpips_host(pred, gt)
+            return out
+        out = {"psnr": self.calculate_psnr(pred, gt), "ssim": self.calculate_ssim(pred, gt)}
         if self.use_lpips:
             out["lpips"] = self.calculate_lpips(pred, gt)
         return out
@@ -258,12 +304,14 @@ _EXTS = {".jpg", ".jpeg", ".png"}
 
 
 def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_lpips: bool = True,
-                  use_fid: bool = True, device: str = "cpu") -> dict:
+                  use_fid: bool = True, device: str = "cpu", lpips_weights=None) -> dict:
     """Match predictions to ground truth by file name (any of .jpg/.jpeg/.png) and aggregate
     mean/std/min/max/median per metric (reference `src/metrics.py:238-348`).  With a `cuda*` device the pairs are
-    scored on the GPU as they are loaded and read back together, one synchronisation per task."""
+    scored on the GPU as they are loaded and read back together, one synchronisation per task.  LPIPS is reported
+    when weights are configured (`lpips_weights` or `IRX_LPIPS_WEIGHTS`); a pair it refuses (a side below 31 px) is
+    skipped whole, as the reference skips a pair whose `calculate_all` raises."""
     pred_dir, gt_dir = Path(pred_dir), Path(gt_dir)
-    calc = MetricsCalculator(use_lpips=use_lpips, use_fid=use_fid, device=device)
+    calc = MetricsCalculator(use_lpips=use_lpips, use_fid=use_fid, device=device, lpips_weights=lpips_weights)
     pred_files = sorted(f for f in pred_dir.iterdir() if f.suffix.lower() in _EXTS)
     gt_names = {f.name for f in gt_dir.iterdir() if f.suffix.lower() in _EXTS}
     if len(pred_files) != len(gt_names):
@@ -282,22 +330,27 @@ def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_
     if not pairs:
         raise ValueError(f"No matching files found between {pred_dir} and {gt_dir}")
     all_metrics = {"psnr": [], "ssim": []}
-    if use_lpips:
+    if calc.use_lpips:
         all_metrics["lpips"] = []
     print(f"Evaluating {task_name}: {len(pairs)} image pairs...")
-    pending = []    # GPU path: (slot in the psnr / ssim lists, device (squared error, SSIM), values per image)
+    # GPU path: (slot in the lists, device (squared error, SSIM[, LPIPS]), values per image, LPIPS on the device)
+    pending = []
     for i, (pp, gp) in enumerate(pairs):
         try:
             pred, gt = load_image(pp), load_image(gp)
-            dev = calc._device_stats(pred, gt)
-            if dev is not None:                 # enqueued; read back after the loop, all pairs in one download
-                pending.append((len(all_metrics["psnr"]),) + dev)
+            pair = calc._device_pair(pred, gt)
+            if pair is not None:                # enqueued; read back after the loop, all pairs in one download
+                # LPIPS first: a pair it refuses raises here, before any slot of the pair exists
+                lp = calc._lpips_pair(pair) if calc.use_lpips else None
+                lp_host = calc._lpips_host(pred, gt) if calc.use_lpips and lp is None else None
+                stats, n = calc._device_stats(pred, gt, pair)
+                if lp is not None:
+                    stats = calc._gpu.torch.cat([stats, lp])
+                pending.append((len(all_metrics["psnr"]), stats, n, lp is not None))
                 all_metrics["psnr"].append(None)
                 all_metrics["ssim"].append(None)
                 if calc.use_lpips:
-                    v = calc.calculate_lpips(pred, gt)
-                    if v is not None:
-                        all_metrics["lpips"].append(v)
+                    all_metrics["lpips"].append(lp_host)
             else:
                 for k, v in calc.calculate_all(pred, gt).items():
                     if v is not None:
@@ -308,10 +361,15 @@ def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_
             print(f"Error processing {pp.name}: {e}")
     if pending:
         G = calc._gpu_module()
-        vals = G.torch.stack([t for _, t, _ in pending]).cpu().numpy()     # the task's one synchronisation
-        for (slot, _, n), v in zip(pending, vals):
+        vals = G.torch.cat([t for _, t, _, _ in pending]).cpu().numpy()    # the task's one synchronisation
+        at = 0
+        for slot, t, n, has_lp in pending:
+            v = vals[at:at + t.numel()]
+            at += t.numel()
             all_metrics["psnr"][slot] = G.psnr_from_sse(int(v[0]), n)
             all_metrics["ssim"][slot] = float(v[1])
+            if has_lp:
+                all_metrics["lpips"][slot] = float(v[2])
     res = {"task": task_name, "num_samples": len(pairs), "metrics": {}}
     for k, vals in all_metrics.items():
         if vals:

@@ -29,6 +29,7 @@ extern "C" {
 #define IRX_MODEL_UNET 0
 #define IRX_MODEL_VAE 1
 #define IRX_MODEL_CLIP 2
+#define IRX_MODEL_LPIPS 3   /* LPIPS(alex) v0.1 (src/metrics.py:97-111): fp32 only, the config is not read */
 
 /* weight layouts of manifest entries (how the host packs diffusers tensors into the blob) */
 #define IRX_LAYOUT_VEC 0   /* [n] fp32, zero padded                                  */
@@ -316,6 +317,28 @@ int irx_metrics_pair_u8(void* stream, const uint8_t* pred, const uint8_t* gt, in
  * (w0 = 2048 - w1); out = clip8((sum + 2^21) >> 22).  Integer, exact. */
 int irx_resize_linear_u8(void* stream, const uint8_t* src, int batch, int H, int W, int C, const int* xtab,
                          const int* ytab, int h, int w, uint8_t* dst);
+
+/* ---- LPIPS(alex) (MetricsCalculator.calculate_lpips, src/metrics.py:97-111; image_to_tensor, :49-55) ----
+ * lpips.LPIPS(net='alex') v0.1 in eval mode, spatial=False, on uint8 RGB pairs: m is an IRX_MODEL_LPIPS model whose
+ * blob holds torchvision's AlexNet `features.{0,3,6,8,10}.{weight,bias}` and the lpips package's
+ * `lin{0..4}.model.1.weight`.  pred / gt [batch][H][W][3] in device memory, H, W >= 31.  in_lut = device
+ * float[256][3]: the scaling layer's output for byte value v in channel c, (float32(v) / 255 * 2 - 1 - shift[c]) /
+ * scale[c] in float32 (lpips_host.input_table).  total[b] = the score, layers[b][k] (NULL: not wanted) = the five
+ * taps' terms; total is their sum in index order.  The trunk runs in exact fp32 (MFMA), the per-pixel head terms are
+ * added in fp64 in a fixed order (block partials, a fixed tree, no atomics): the same bits on every run.
+ * ws: irx_lpips_workspace_bytes(m, batch, H, W) bytes of device memory, 16-byte aligned.  A refused argument (null
+ * pointer, batch <= 0, H or W < 31, a model of another kind or without a bound blob, a short workspace) is a status
+ * and launches nothing.  Enqueues on `stream`: no allocation, no synchronisation. */
+int irx_lpips_workspace_bytes(const irx_model* m, int batch, int H, int W, size_t* bytes);
+int irx_lpips_u8(irx_model* m, void* stream, const uint8_t* pred, const uint8_t* gt, int batch, int H, int W,
+                 const float* in_lut, double* total, double* layers, void* ws, size_t ws_bytes);
+/* the two data-movement kernels of the LPIPS trunk on their own (tests): the input conversion of irx_lpips_u8 into
+ * out fp32 [2 batch][H][W][4] (pred images first, channel 3 zero), and ReLU followed by a win x win / stride max pool
+ * without padding, (win, stride) = (3, 2) or (1, 1), over fp32 NHWC x [n][H][W][C], C % 4 == 0, into
+ * out [n][(H - win) / stride + 1][(W - win) / stride + 1][C] */
+int irx_op_lpips_input(void* stream, const uint8_t* pred, const uint8_t* gt, int batch, int H, int W,
+                       const float* in_lut, float* out);
+int irx_op_lpips_relu_pool(void* stream, const float* x, int n, int H, int W, int C, int win, int stride, float* out);
 
 /* ---- multi-GPU: RCCL over xGMI (SURVEY.md §8b `irx_weights_bcast(handle, rcclComm)`, §8e) ----
    The reference has no multi-device path (src/inference.py:52-57 picks one device; it stands in for
