@@ -34,6 +34,8 @@ PER_FILE = {"elementwise.hip": ["-ffp-contract=off"],
             "metrics.hip": ["-ffp-contract=off"],
             # the LPIPS head as lpips_host.py writes it: divisions, squares and sums as separate operations
             "lpips.hip": ["-ffp-contract=off"],
+            # the FID glue as fid_host.py writes it: x * a + b, tap products and sums as separate operations
+            "fid.hip": ["-ffp-contract=off"],
             # Pillow's coefficient doubles: libm's sin, IEEE divisions, no FMA (csrc/resample_coeffs.cpp)
             "resample_coeffs.cpp": ["-ffp-contract=off", "-fno-fast-math"]}
 

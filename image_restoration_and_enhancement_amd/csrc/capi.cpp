@@ -230,6 +230,7 @@ int irx_model_create(int kind, const irx_model_config* cfg, int dtype, irx_model
     else if (kind == IRX_MODEL_VAE) h->m.reset(new Vae(*cfg, dtype));
     else if (kind == IRX_MODEL_CLIP) h->m.reset(new Clip(*cfg, dtype));
     else if (kind == IRX_MODEL_LPIPS) h->m.reset(new LpipsAlex(*cfg, dtype));
+    else if (kind == IRX_MODEL_FID) h->m.reset(new InceptionFid(*cfg, dtype));
     else throw Error("unknown model kind");
   } catch (...) {
     delete h;
@@ -673,6 +674,63 @@ int irx_op_lpips_relu_pool(void* s, const float* x, int n, int H, int W, int C, 
   IRX_CHECK(x && out && x != out, "null buffer");
   IRX_CHECK(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0, "buffers must be 16-byte aligned");
   lpips_relu_pool(x, n, H, W, C, win, stride, out, S(s));
+  IRX_API_END
+}
+// ------------------------------------------------------------------ FID features (fid_model.cpp, fid.hip;
+// MetricsCalculator.get_inception_features, src/metrics.py:150-165)
+int irx_fid_workspace_bytes(const irx_model* m, int B, int H, int W, size_t* bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(bytes, "null argument");
+  *bytes = const_cast<InceptionFid*>(as<InceptionFid>(m, IRX_MODEL_FID))->workspace_bytes(B, H, W);
+  IRX_API_END
+}
+int irx_fid_features(irx_model* m, void* s, const float* x, int B, int H, int W, float* out, void* ws,
+                     size_t ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(x && out && ws, "null input, output or workspace pointer");
+  IRX_CHECK(B > 0, "batch must be positive");
+  IRX_CHECK(H >= InceptionFid::kMinSide && W >= InceptionFid::kMinSide, "FID: H, W >= 75");
+  as<InceptionFid>(m, IRX_MODEL_FID)->features(S(s), x, B, H, W, out, (char*)ws, ws_bytes);
+  IRX_API_END
+}
+int irx_op_fid_input(void* s, const uint8_t* img, int H, int W, const int* xstart, const int* xcount,
+                     const float* xweight, int kx, const int* ystart, const int* ycount, const float* yweight, int ky,
+                     float* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(img && xstart && xcount && xweight && ystart && ycount && yweight && out, "null buffer");
+  IRX_CHECK(((uintptr_t)out % 16) == 0, "output must be 16-byte aligned");
+  fid_input(img, H, W, xstart, xcount, xweight, kx, ystart, ycount, yweight, ky, out, S(s));
+  IRX_API_END
+}
+int irx_op_fid_bn_relu(void* s, const float* x, long rows, int C, const float* scale, const float* shift, float* out,
+                       int ldo, int coff) {
+  IRX_API_BEGIN
+  IRX_CHECK(x && scale && shift && out, "null buffer");
+  IRX_CHECK(coff >= 0 && coff % 4 == 0 && C > 0 && coff + C <= ldo, "slice [coff, coff + C) must lie inside a row");
+  IRX_CHECK(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)scale % 16) == 0 &&
+            ((uintptr_t)shift % 16) == 0, "buffers must be 16-byte aligned");
+  fid_bn_relu(x, rows, C, scale, shift, out + coff, ldo, S(s));
+  IRX_API_END
+}
+int irx_op_fid_avgpool3(void* s, const float* x, int n, int H, int W, int C, float* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(x && out && x != out, "null buffer");
+  IRX_CHECK(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0, "buffers must be 16-byte aligned");
+  fid_avgpool3(x, n, H, W, C, out, S(s));
+  IRX_API_END
+}
+int irx_op_fid_maxpool3s2(void* s, const float* x, int n, int H, int W, int C, float* out, int ldo, int coff) {
+  IRX_API_BEGIN
+  IRX_CHECK(x && out && x != out, "null buffer");
+  IRX_CHECK(coff >= 0 && coff % 4 == 0 && C > 0 && coff + C <= ldo, "slice [coff, coff + C) must lie inside a row");
+  IRX_CHECK(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0, "buffers must be 16-byte aligned");
+  fid_maxpool3s2(x, n, H, W, C, out + coff, ldo, S(s));
+  IRX_API_END
+}
+int irx_op_fid_gap(void* s, const float* x, int B, int hw, int C, float* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(x && out && x != out, "null buffer");
+  fid_gap(x, B, hw, C, out, S(s));
   IRX_API_END
 }
 // ------------------------------------------------------------------ single ops

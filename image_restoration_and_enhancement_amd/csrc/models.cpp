@@ -112,20 +112,22 @@ Act Model::new_act(Ctx& c, int n, int h, int w, int ch) {
   return a;
 }
 
-static GemmArgs conv_args(int dt, const Act& x0, const Act* x1, const void* w, const float* b, int cout, int k,
-                          int stride, int pad_t, int pad_l, int hv, int wv, const Act& out, const float* rowadd,
-                          long rowadd_ld, const void* residual, int out_f32, int ldc) {
+// kh x kw kernel; the square form below is what every caller but InceptionV3's (1, 7) / (7, 1) / (1, 3) / (3, 1)
+// units uses
+static GemmArgs conv_args(int dt, const Act& x0, const Act* x1, const void* w, const float* b, int cout, int kh,
+                          int kw, int stride, int pad_t, int pad_l, int hv, int wv, const Act& out,
+                          const float* rowadd, long rowadd_ld, const void* residual, int out_f32, int ldc) {
   GemmArgs a;
   a.dtype = dt;
   a.conv = 1;
   a.g.src0 = x0.p; a.g.C0 = x0.c;
   a.g.src1 = x1 ? x1->p : nullptr; a.g.C1 = x1 ? x1->c : 0;
   a.g.N = x0.n; a.g.Hin = x0.h; a.g.Win = x0.w; a.g.Hv = hv; a.g.Wv = wv;
-  a.g.KH = k; a.g.KW = k; a.g.stride = stride; a.g.pad_t = pad_t; a.g.pad_l = pad_l;
+  a.g.KH = kh; a.g.KW = kw; a.g.stride = stride; a.g.pad_t = pad_t; a.g.pad_l = pad_l;
   a.g.Ho = out.h; a.g.Wo = out.w;
   a.M = out.n * out.h * out.w;
   a.N = cout;
-  a.K = k * k * (a.g.C0 + a.g.C1);
+  a.K = kh * kw * (a.g.C0 + a.g.C1);
   a.B = w; a.ldb = a.K;
   a.C = out.p; a.ldc = ldc < 0 ? cout : ldc;
   a.out_f32 = out_f32;
@@ -135,6 +137,13 @@ static GemmArgs conv_args(int dt, const Act& x0, const Act* x1, const void* w, c
   a.imgs = out.n;
   conv1x1_as_dense(a);   // 1x1 convs (ff chains, resnet shortcuts) on the dense GEMM path
   return a;
+}
+
+static GemmArgs conv_args(int dt, const Act& x0, const Act* x1, const void* w, const float* b, int cout, int k,
+                          int stride, int pad_t, int pad_l, int hv, int wv, const Act& out, const float* rowadd,
+                          long rowadd_ld, const void* residual, int out_f32, int ldc) {
+  return conv_args(dt, x0, x1, w, b, cout, k, k, stride, pad_t, pad_l, hv, wv, out, rowadd, rowadd_ld, residual,
+                   out_f32, ldc);
 }
 
 void Model::gn_conv3(Ctx& c, const Act& x0, const Act* x1, P g, P gb, float eps, int silu, P w, P b, int cout,
@@ -168,6 +177,13 @@ void Model::conv2d(Ctx& c, const Act& x0, const Act* x1, P w, P b, int cout, int
                          rowadd, rowadd_ld, residual, out_f32, ldc);
   a.res_rows = res_rows;
   run_gemm(c, a, stats && ldc < 0 ? &out : nullptr);
+}
+
+void Model::conv2d(Ctx& c, const Act& x, P w, int cout, int kh, int kw, int stride, int pad_t, int pad_l, Act& out,
+                   int ldc) {
+  GemmArgs a = conv_args(dt_, x, nullptr, ptr(w), nullptr, cout, kh, kw, stride, pad_t, pad_l, x.h, x.w, out, nullptr,
+                         0, nullptr, 0, ldc);
+  run_gemm(c, a, nullptr);
 }
 
 void Model::run_gemm(Ctx& c, GemmArgs& a, Act* stats) {

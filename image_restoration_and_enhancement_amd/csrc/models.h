@@ -1,4 +1,4 @@
-// irx — native model graphs (UNet2DConditionModel, AutoencoderKL, CLIPTextModel, LPIPS AlexNet) over the irx kernels.
+// irx — native model graphs (UNet2DConditionModel, AutoencoderKL, CLIPTextModel, LPIPS AlexNet, FID InceptionV3) over the irx kernels.
 #pragma once
 #include <map>
 #include <memory>
@@ -93,6 +93,9 @@ class Model {
               int hv, int wv, Act& out, const float* rowadd = nullptr, long rowadd_ld = 0,
               const void* residual = nullptr, int out_f32 = 0, int ldc = -1, bool stats = false,
               long res_rows = 0);
+  // the same with a kh x kw kernel ((1, 7), (7, 1), (1, 3), (3, 1) of InceptionV3): no bias, no epilogue extras
+  void conv2d(Ctx& c, const Act& x, P w, int cout, int kh, int kw, int stride, int pad_t, int pad_l, Act& out,
+              int ldc = -1);
   void linear(Ctx& c, const void* A, long lda, int M, int K, P w, int N, const float* bias, void* C, long ldc,
               int act = ACT_NONE, const void* residual = nullptr, long ldr = 0, int out_f32 = 0, int imgs = 0,
               Act* stats = nullptr, long res_rows = 0);
@@ -253,6 +256,36 @@ class LpipsAlex : public Model {
   void run(Ctx& c, const uint8_t* pred, const uint8_t* gt, int B, int H, int W, const float* lut, double* total,
            double* layers);
   P cw_[5], cb_[5], lw_[5];
+};
+
+// torchvision's InceptionV3 trunk in eval mode up to the 2048 pooled features (fid_host.py; the reference's
+// src/metrics.py:70-80, 150-223): every BasicConv2d as a bias-free conv on gemm()'s exact-f32 path followed by
+// fid_bn_relu with the host-folded BatchNorm scale / shift; a branch's last unit writes its slice of the block's
+// concat buffer.  fp32 only; the config is not read.
+class InceptionFid : public Model {
+ public:
+  InceptionFid(const irx_model_config& cfg, int dtype);
+  static constexpr int kMinSide = 75;   // below it Mixed_7a's pool has no window left
+  static constexpr int kFeatures = 2048;
+  size_t workspace_bytes(int B, int H, int W);
+  // x fp32 NHWC4 [B][H][W][4] (channel 3 zero); out fp32 [B][2048]
+  void features(hipStream_t s, const float* x, int B, int H, int W, float* out, char* ws, size_t cap);
+
+ private:
+  struct Unit { P w, sc, sh; int cin, cout, kh, kw, stride, ph, pw; };
+  int unit(const std::string& name, int cin, int cout, int kh, int kw, int stride = 1, int ph = 0, int pw = 0);
+  Act cbr(Ctx& c, const Act& x, int& u);                       // the next unit into a new activation
+  void cbr_into(Ctx& c, const Act& x, int& u, Act& cat, int off);   // ... into channels [off, off + cout) of cat
+  Act avgpool(Ctx& c, const Act& x);
+  Act stem_pool(Ctx& c, Act& x);
+  void maxpool_into(Ctx& c, const Act& x, Act& cat, int off);
+  Act block_a(Ctx& c, Act& x, int& u);
+  Act block_b(Ctx& c, Act& x, int& u);
+  Act block_c(Ctx& c, Act& x, int& u);
+  Act block_d(Ctx& c, Act& x, int& u);
+  Act block_e(Ctx& c, Act& x, int& u);
+  void run(Ctx& c, const float* x, int B, int H, int W, float* out);
+  std::vector<Unit> units_;
 };
 
 }  // namespace irx

@@ -379,4 +379,21 @@ int lpips_head_blocks(int hw);   // partials per image of a tap with hw pixels
 void lpips_head(const float* f, int B, int hw, int C, const float* w, int tap, double* part, double* lay,
                 double* layers, double* total, hipStream_t s);
 
+// ------------------------------------------------------------ FID (fid.hip; the trunk: InceptionFid, models.h)
+constexpr int FID_SIDE = 299;
+// one uint8 [H][W][3] image -> out fp32 [299][299][4]: /255, the antialiased bilinear resize (width pass, then height
+// pass, per output tile from LDS), (v - mean) / std, channel 3 zero.  Tap tables of fid_host.aa_taps in device memory:
+// start / count int[299], weights float[299][kmax] per axis.  Table entries are clamped to the image in the kernel.
+void fid_input(const uint8_t* img, int H, int W, const int* xs, const int* xn, const float* xw, int kx, const int* ys,
+               const int* yn, const float* yw, int ky, float* out, hipStream_t s);
+// y[r][off + c] = max(x[r][c] * a[c] + b[c], 0) for x fp32 [rows][C]; y rows are ldo floats apart (y already points
+// at channel `off` of the concat buffer).  C, ldo % 4 == 0.  x == y with ldo == C is allowed.
+void fid_bn_relu(const float* x, long rows, int C, const float* a, const float* b, float* y, int ldo, hipStream_t s);
+// 3 x 3 / stride 1 / pad 1 average, always / 9 (count_include_pad); fp32 NHWC, C % 4 == 0
+void fid_avgpool3(const float* x, int N, int H, int W, int C, float* y, hipStream_t s);
+// 3 x 3 / stride 2 max without padding into rows ldo floats apart (y points at the slice's first channel)
+void fid_maxpool3s2(const float* x, int N, int H, int W, int C, float* y, int ldo, hipStream_t s);
+// mean over the hw pixels of x fp32 [B][hw][C] -> y [B][C]: pixel order, one division
+void fid_gap(const float* x, int B, int hw, int C, float* y, hipStream_t s);
+
 }  // namespace irx

@@ -17,8 +17,14 @@ arithmetic restated:
 
 PSNR / SSIM / rgb2lab are pinned against scikit-image 0.18.3 outputs committed under
 `tests/golden/metrics.json` (tests/test_metrics.py).  The INTER_LINEAR resize and JPEG decode are
-restatements without an oracle in this image (cv2 is absent): parity unpinned.  FID needs a network-downloaded
-InceptionV3 and stays unavailable, exactly as the reference behaves without torchvision (`src/metrics.py:24-37`).
+restatements without an oracle in this image (cv2 is absent): parity unpinned.
+
+FID (`src/metrics.py:150-223`) is computed when the user points at torchvision's InceptionV3 checkpoint —
+`fid_weights=` or the environment variable `IRX_FID_WEIGHTS` (`fid_host.load_weights`); the code is `fid_host`
+(plain torch) on the host and `fid_gpu` (csrc/fid_model.cpp, csrc/fid.hip) with `device="cuda"`; the distance itself
+is the reference's numpy / scipy arithmetic (`fid_host.frechet_distance`).  With nothing configured the metric is off
+as before: `use_fid` is False, `calculate_fid` returns None, `evaluate_task` reports no `fid` entry, and the module
+constant `FID_AVAILABLE` (torchvision itself) stays False.  A path that is set but cannot be read is an error.
 
 LPIPS(alex) (`src/metrics.py:97-111`) is computed when the user points at the two weight files it needs —
 `lpips_weights=` or the environment variable `IRX_LPIPS_WEIGHTS` (a directory or a file, `lpips_host.load_weights`);
@@ -42,6 +48,7 @@ from scipy.ndimage import uniform_filter
 LPIPS_AVAILABLE = False
 FID_AVAILABLE = False
 LPIPS_WEIGHTS_ENV = "IRX_LPIPS_WEIGHTS"
+FID_WEIGHTS_ENV = "IRX_FID_WEIGHTS"
 
 # skimage.color: sRGB (D65) -> XYZ and the D65 / 2-degree white point
 _XYZ_FROM_RGB = np.array([[0.412453, 0.357580, 0.180423],
@@ -169,19 +176,83 @@ def resolve_lpips_weights(lpips_weights=None):
     return lpips_host.check_weights(src) if isinstance(src, dict) else lpips_host.load_weights(src)
 
 
+def resolve_fid_weights(fid_weights=None):
+    """The InceptionV3 weights as a checked dict, or None when nothing is configured: `fid_weights` (a dict of
+    tensors, or a directory / file for `fid_host.load_weights`), else the path in `IRX_FID_WEIGHTS`.  A source that
+    is given but cannot be read raises."""
+    src = fid_weights if fid_weights is not None else (os.environ.get(FID_WEIGHTS_ENV) or None)
+    if src is None:
+        return None
+    from . import fid_host
+    return fid_host.check_weights(src) if isinstance(src, dict) else fid_host.load_weights(src)
+
+
+class _FidCollector:
+    """The Inception features of a growing set of (pred, gt) pairs without keeping the images: on the GPU through
+    `fid_gpu.FeatureQueue` (one queue per side, enqueued, nothing waits), else `fid_host` in float32 right away."""
+
+    def __init__(self, calc: "MetricsCalculator"):
+        self.calc = calc
+        self.net = calc._fid_network()
+        self.host = ([], [])
+        self.queues = None
+        if self.net is not None:
+            from . import fid_gpu
+            self.queues = (fid_gpu.FeatureQueue(self.net), fid_gpu.FeatureQueue(self.net))
+
+    def add(self, pred, gt) -> None:
+        """One pair; `pred` goes to gt's size first (cv2.resize in the reference, `src/metrics.py:190-191`)."""
+        calc = self.calc
+        if self.queues is not None and all(len(x.shape) == 3 and x.shape[2] == 3 for x in (pred, gt)):
+            G = calc._gpu_module()
+            p, g = G.to_device(pred, calc.device), G.to_device(gt, calc.device)
+            if tuple(p.shape[:2]) != tuple(g.shape[:2]):
+                p = G.resize_linear_u8(p, g.shape[1], g.shape[0])
+            self.queues[0].add(p)
+            self.queues[1].add(g)
+            return
+        from . import fid_host
+        pred, gt = _to_host(pred), _to_host(gt)
+        if pred.shape[:2] != gt.shape[:2]:
+            pred = resize_linear(pred, gt.shape[1], gt.shape[0])
+        for side, im in zip(self.host, (pred, gt)):
+            side.append(fid_host.features_u8([im], calc._fid_w))
+
+    def device_features(self):
+        """Device float32 [2, n, 2048] of the pairs that went through the GPU (pred set, gt set), or None."""
+        if self.queues is None or len(self.queues[0]) == 0:
+            return None
+        return self.calc._gpu.torch.stack([q.finish() for q in self.queues])
+
+    def score(self, dev_feats=None) -> float:
+        """The Fréchet distance of everything collected; `dev_feats` is `device_features()` already on the host."""
+        import torch
+        sets = []
+        for k in range(2):
+            parts = list(self.host[k])
+            if dev_feats is not None:
+                parts.append(torch.as_tensor(np.asarray(dev_feats[k], dtype=np.float32)))
+            sets.append(torch.cat(parts, 0).numpy())
+        from . import fid_host
+        return fid_host.frechet_distance(sets[0], sets[1])
+
+
 class MetricsCalculator:
-    """Per-image metrics (reference `src/metrics.py:57-209`).  FID: unavailable offline.  LPIPS(alex): on when
-    weights are configured (`lpips_weights` or `IRX_LPIPS_WEIGHTS`), see the module docstring.
+    """Per-image metrics (reference `src/metrics.py:57-209`).  LPIPS(alex) and FID: on when their weights are
+    configured (`lpips_weights` / `IRX_LPIPS_WEIGHTS`, `fid_weights` / `IRX_FID_WEIGHTS`), see the module docstring.
 
     `device="cpu"` (the default) is the numpy code above.  A `cuda*` string or torch.device scores on the GPU
     (`metrics_gpu`, csrc/metrics.hip) when one is visible, `libirx.so` loads and the pair's shape is inside the
     kernel's range (H, W >= 7, 1 or 3 channels); any other pair takes the numpy code.  Every method accepts numpy
     images or uint8 device tensors ([H, W] or [H, W, C]), so `restore_batch` outputs are scored without a download."""
 
-    def __init__(self, use_lpips: bool = True, use_fid: bool = True, device: str = "cpu", lpips_weights=None):
+    def __init__(self, use_lpips: bool = True, use_fid: bool = True, device: str = "cpu", lpips_weights=None,
+                 fid_weights=None):
         self._lpips_w = resolve_lpips_weights(lpips_weights) if use_lpips else None
         self.use_lpips = self._lpips_w is not None
-        self.use_fid = use_fid and FID_AVAILABLE
+        self._fid_w = resolve_fid_weights(fid_weights) if use_fid else None
+        self.use_fid = self._fid_w is not None
+        self._fid_net = None    # fid_gpu.InceptionFeatures, made at the first GPU feature call
         self.device = device
         self._gpu = False       # metrics_gpu, None (host), or False: not decided yet
         self._lpips_net = None  # lpips_gpu.LpipsAlex, made at the first GPU score
@@ -281,8 +352,30 @@ class MetricsCalculator:
         gl = rgb2lab(gt.astype(np.float32) / 255.0)
         return float(np.mean(np.sqrt(np.sum((pl - gl) ** 2, axis=2))))
 
+    def _fid_network(self):
+        """`fid_gpu.InceptionFeatures` when `device` names a visible GPU and the native library loads; else None."""
+        if self._gpu_module() is None:
+            return None
+        if self._fid_net is None:
+            from . import fid_gpu
+            self._fid_net = fid_gpu.InceptionFeatures(self._fid_w, self.device)
+        return self._fid_net
+
     def calculate_fid(self, pred_images, gt_images):
-        return None
+        """FID of two image sets (reference `src/metrics.py:164-223`), or None when no weights are configured.
+        Images are uint8 RGB numpy arrays or device tensors of any sizes; features come from the GPU with a `cuda*`
+        device (one download of the two [N, 2048] sets), else from `fid_host` in float32."""
+        if not self.use_fid:
+            return None
+        if len(pred_images) != len(gt_images):
+            print(f"Warning: FID requires equal number of images. Got {len(pred_images)} pred vs {len(gt_images)} gt")
+            return None
+        print("  Extracting Inception features for FID...")
+        col = _FidCollector(self)
+        for pred, gt in zip(pred_images, gt_images):
+            col.add(pred, gt)
+        dev = col.device_features()
+        return col.score(None if dev is None else dev.cpu().numpy())
 
     def calculate_all(self, pred: np.ndarray, gt: np.ndarray) -> dict:
         pair = self._device_pair(pred, gt)      # one upload, the resize if the shapes differ
@@ -304,14 +397,17 @@ _EXTS = {".jpg", ".jpeg", ".png"}
 
 
 def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_lpips: bool = True,
-                  use_fid: bool = True, device: str = "cpu", lpips_weights=None) -> dict:
+                  use_fid: bool = True, device: str = "cpu", lpips_weights=None, fid_weights=None) -> dict:
     """Match predictions to ground truth by file name (any of .jpg/.jpeg/.png) and aggregate
     mean/std/min/max/median per metric (reference `src/metrics.py:238-348`).  With a `cuda*` device the pairs are
     scored on the GPU as they are loaded and read back together, one synchronisation per task.  LPIPS is reported
     when weights are configured (`lpips_weights` or `IRX_LPIPS_WEIGHTS`); a pair it refuses (a side below 31 px) is
-    skipped whole, as the reference skips a pair whose `calculate_all` raises."""
+    skipped whole, as the reference skips a pair whose `calculate_all` raises.  FID is reported (`fid`, one value)
+    when weights are configured (`fid_weights` or `IRX_FID_WEIGHTS`): each scored pair's Inception features are
+    taken as the loop runs — the reference keeps every image in a list instead — and read back with the rest."""
     pred_dir, gt_dir = Path(pred_dir), Path(gt_dir)
-    calc = MetricsCalculator(use_lpips=use_lpips, use_fid=use_fid, device=device, lpips_weights=lpips_weights)
+    calc = MetricsCalculator(use_lpips=use_lpips, use_fid=use_fid, device=device, lpips_weights=lpips_weights,
+                             fid_weights=fid_weights)
     pred_files = sorted(f for f in pred_dir.iterdir() if f.suffix.lower() in _EXTS)
     gt_names = {f.name for f in gt_dir.iterdir() if f.suffix.lower() in _EXTS}
     if len(pred_files) != len(gt_names):
@@ -335,6 +431,12 @@ def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_
     print(f"Evaluating {task_name}: {len(pairs)} image pairs...")
     # GPU path: (slot in the lists, device (squared error, SSIM[, LPIPS]), values per image, LPIPS on the device)
     pending = []
+    fid, fid_error = None, None
+    if calc.use_fid:
+        try:
+            fid = _FidCollector(calc)
+        except Exception as e:
+            fid_error = e
     for i, (pp, gp) in enumerate(pairs):
         try:
             pred, gt = load_image(pp), load_image(gp)
@@ -355,13 +457,32 @@ def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_
                 for k, v in calc.calculate_all(pred, gt).items():
                     if v is not None:
                         all_metrics[k].append(v)
+            if fid is not None and fid_error is None:       # after the pair's own metrics: a skipped pair is not in
+                try:                                        # the tensors already on the device, where there are any
+                    fid.add(*(pair if pair is not None else (pred, gt)))
+                except Exception as e:
+                    fid_error = e
             if (i + 1) % 10 == 0:
                 print(f"  Processed {i + 1}/{len(pairs)}")
         except Exception as e:  # the reference skips unreadable pairs
             print(f"Error processing {pp.name}: {e}")
+    fid_dev = None
+    if fid is not None and fid_error is None:
+        try:
+            fid_dev = fid.device_features()
+        except Exception as e:
+            fid_error = e
+    fid_host_feats = None
+    if fid_dev is not None and not pending:
+        fid_host_feats = fid_dev.cpu().numpy()
     if pending:
         G = calc._gpu_module()
-        vals = G.torch.cat([t for _, t, _, _ in pending]).cpu().numpy()    # the task's one synchronisation
+        parts = [t for _, t, _, _ in pending]
+        if fid_dev is not None:             # float32 -> float64 is exact: the features ride in the same download
+            parts.append(fid_dev.reshape(-1).to(parts[0].dtype))
+        vals = G.torch.cat(parts).cpu().numpy()                            # the task's one synchronisation
+        if fid_dev is not None:
+            fid_host_feats = vals[-fid_dev.numel():].reshape(tuple(fid_dev.shape))
         at = 0
         for slot, t, n, has_lp in pending:
             v = vals[at:at + t.numel()]
@@ -370,6 +491,14 @@ def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_
             all_metrics["ssim"][slot] = float(v[1])
             if has_lp:
                 all_metrics["lpips"][slot] = float(v[2])
+    if calc.use_fid:
+        print("\n  Calculating FID (dataset-level metric)...")
+        try:
+            if fid_error is not None:
+                raise fid_error
+            all_metrics["fid"] = [fid.score(fid_host_feats)]    # stored as a list, as the reference does
+        except Exception as e:
+            print(f"  Warning: FID calculation failed: {e}")
     res = {"task": task_name, "num_samples": len(pairs), "metrics": {}}
     for k, vals in all_metrics.items():
         if vals:

@@ -30,6 +30,7 @@ extern "C" {
 #define IRX_MODEL_VAE 1
 #define IRX_MODEL_CLIP 2
 #define IRX_MODEL_LPIPS 3   /* LPIPS(alex) v0.1 (src/metrics.py:97-111): fp32 only, the config is not read */
+#define IRX_MODEL_FID 4     /* InceptionV3 pooled features (src/metrics.py:70-80): fp32 only, the config is not read */
 
 /* weight layouts of manifest entries (how the host packs diffusers tensors into the blob) */
 #define IRX_LAYOUT_VEC 0   /* [n] fp32, zero padded                                  */
@@ -339,6 +340,39 @@ int irx_lpips_u8(irx_model* m, void* stream, const uint8_t* pred, const uint8_t*
 int irx_op_lpips_input(void* stream, const uint8_t* pred, const uint8_t* gt, int batch, int H, int W,
                        const float* in_lut, float* out);
 int irx_op_lpips_relu_pool(void* stream, const float* x, int n, int H, int W, int C, int win, int stride, float* out);
+
+/* ---- FID features (MetricsCalculator.get_inception_features / calculate_fid, src/metrics.py:150-223; the model and
+ * its transform, :70-80) ----
+ * torchvision's inception_v3(transform_input=False) in eval mode with fc = Identity: m is an IRX_MODEL_FID model whose
+ * blob holds every trunk unit's `<unit>.conv.weight` and the BatchNorm of the unit folded on the host into
+ * `<unit>.bn.scale` = gamma / sqrt(var + 1e-3) and `<unit>.bn.shift` = beta - mean * scale (fid_host.fold_bn, fp64,
+ * stored fp32).  x fp32 NHWC [batch][H][W][4] in device memory, channel 3 zero, H, W >= 75 (the metric feeds 299 x 299
+ * from irx_op_fid_input); out fp32 [batch][2048].  The convolutions run in exact fp32 (MFMA); no atomics anywhere: the
+ * same bits on every run, and an image's features do not depend on its position in the batch or on the batch size.
+ * ws: irx_fid_workspace_bytes(m, batch, H, W) bytes, 16-byte aligned.  A refused argument (null pointer, batch <= 0, a
+ * side below 75, a model of another kind or without a bound blob, a short workspace) is a status and launches nothing.
+ * Enqueues on `stream`: no allocation, no synchronisation. */
+int irx_fid_workspace_bytes(const irx_model* m, int batch, int H, int W, size_t* bytes);
+int irx_fid_features(irx_model* m, void* stream, const float* x, int batch, int H, int W, float* out, void* ws,
+                     size_t ws_bytes);
+/* The trunk's glue kernels on their own (tests).
+ * irx_op_fid_input: ToTensor, transforms.Resize((299, 299)) on the tensor (bilinear, antialias) and Normalize of
+ * src/metrics.py:74-80 for one uint8 [H][W][3] image -> out fp32 [299][299][4], channel 3 zero.  xstart / xcount
+ * int[299] and xweight float[299][kx] are the width taps, the y tables the height taps (fid_host.aa_taps); the width
+ * pass runs first, as ATen's.
+ * irx_op_fid_bn_relu: out[r][coff + c] = max(x[r][c] * scale[c] + shift[c], 0), x fp32 [rows][C], out rows ldo floats.
+ * irx_op_fid_avgpool3: F.avg_pool2d(x, 3, 1, 1) (always / 9) over fp32 NHWC.
+ * irx_op_fid_maxpool3s2: F.max_pool2d(x, 3, 2) over fp32 NHWC into out[n][ho][wo] rows of ldo floats at channel coff.
+ * irx_op_fid_gap: the mean over the hw pixels of x fp32 [batch][hw][C], added in pixel order, one division.
+ * C, ldo and coff are multiples of 4; buffers 16-byte aligned. */
+int irx_op_fid_input(void* stream, const uint8_t* img, int H, int W, const int* xstart, const int* xcount,
+                     const float* xweight, int kx, const int* ystart, const int* ycount, const float* yweight, int ky,
+                     float* out);
+int irx_op_fid_bn_relu(void* stream, const float* x, long rows, int C, const float* scale, const float* shift,
+                       float* out, int ldo, int coff);
+int irx_op_fid_avgpool3(void* stream, const float* x, int n, int H, int W, int C, float* out);
+int irx_op_fid_maxpool3s2(void* stream, const float* x, int n, int H, int W, int C, float* out, int ldo, int coff);
+int irx_op_fid_gap(void* stream, const float* x, int batch, int hw, int C, float* out);
 
 /* ---- multi-GPU: RCCL over xGMI (SURVEY.md §8b `irx_weights_bcast(handle, rcclComm)`, §8e) ----
    The reference has no multi-device path (src/inference.py:52-57 picks one device; it stands in for
