@@ -16,6 +16,7 @@ IRX_F32, IRX_BF16, IRX_F16 = 0, 1, 2
 IRX_MODEL_UNET, IRX_MODEL_VAE, IRX_MODEL_CLIP = 0, 1, 2
 IRX_MODEL_LPIPS = 3       # LPIPS(alex), the reference's src/metrics.py:97-111
 IRX_MODEL_FID = 4         # InceptionV3 pooled features, the reference's src/metrics.py:70-80
+IRX_MODEL_SRVGG = 5       # Real-ESRGAN's SRVGGNetCompact, the reference's src/inference.py:335-336, :579-591
 IRX_LAYOUT_VEC, IRX_LAYOUT_MAT, IRX_LAYOUT_CONV, IRX_LAYOUT_EMB = 0, 1, 2, 3
 IRX_LAYOUT_MAT_GEGLU64, IRX_LAYOUT_VEC_GEGLU64 = 4, 5
 IRX_LAYOUT_VEC_LN_U, IRX_LAYOUT_VEC_LN_V = 6, 7
@@ -145,6 +146,12 @@ _SIGS = {
     "irx_op_fid_avgpool3": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "irx_op_fid_maxpool3s2": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, i32]),
     "irx_op_fid_gap": (i32, [vp, vp, i32, i32, i32, vp]),
+    # Real-ESRGAN (SRVGGNetCompact): RestorationPipeline._sr_realesrgan, src/inference.py:579-591
+    "irx_srvgg_workspace_bytes": (i32, [vp, i32, i32, i32, C.POINTER(sz)]),
+    "irx_srvgg_u8": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz]),
+    "irx_op_srvgg_conv": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "irx_op_srvgg_tail": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "irx_op_srvgg_prelu": (i32, [vp, i32, vp, i64, i32, vp, vp]),
     "irx_op_conv2d": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32,
                             i32, i32, i32, vp, i64, vp, vp, i32, i32]),
     "irx_op_gemm": (i32, [vp, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, f32, i32, vp, i64, i32, i32, i64,

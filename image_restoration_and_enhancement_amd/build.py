@@ -36,6 +36,8 @@ PER_FILE = {"elementwise.hip": ["-ffp-contract=off"],
             "lpips.hip": ["-ffp-contract=off"],
             # the FID glue as fid_host.py writes it: x * a + b, tap products and sums as separate operations
             "fid.hip": ["-ffp-contract=off"],
+            # the SRVGG epilogues and tail as srvgg_host.py writes them: slope * v, + bias, + x, * 255 each on its own
+            "srvgg.hip": ["-ffp-contract=off"],
             # Pillow's coefficient doubles: libm's sin, IEEE divisions, no FMA (csrc/resample_coeffs.cpp)
             "resample_coeffs.cpp": ["-ffp-contract=off", "-fno-fast-math"]}
 

@@ -128,6 +128,8 @@ static const struct { const char* name; int* i; bool* b; } kOpts[] = {
     {"attn_hm", &g_attn_hm, nullptr},
     {"gemm_small_kmax", &g_gemm_small_kmax, nullptr},
     {"nlm2_strip", &g_nlm2_strip, nullptr},
+    {"srvgg_fused", &g_srvgg_fused, nullptr},
+    {"srvgg_blocks", &g_srvgg_blocks, nullptr},
 };
 static OptRef opt_ref(const std::string& n) {
   for (const auto& o : kOpts)
@@ -231,6 +233,7 @@ int irx_model_create(int kind, const irx_model_config* cfg, int dtype, irx_model
     else if (kind == IRX_MODEL_CLIP) h->m.reset(new Clip(*cfg, dtype));
     else if (kind == IRX_MODEL_LPIPS) h->m.reset(new LpipsAlex(*cfg, dtype));
     else if (kind == IRX_MODEL_FID) h->m.reset(new InceptionFid(*cfg, dtype));
+    else if (kind == IRX_MODEL_SRVGG) h->m.reset(new Srvgg(*cfg, dtype));
     else throw Error("unknown model kind");
   } catch (...) {
     delete h;
@@ -731,6 +734,45 @@ int irx_op_fid_gap(void* s, const float* x, int B, int hw, int C, float* out) {
   IRX_API_BEGIN
   IRX_CHECK(x && out && x != out, "null buffer");
   fid_gap(x, B, hw, C, out, S(s));
+  IRX_API_END
+}
+// ------------------------------------------------------------------ Real-ESRGAN SRVGGNetCompact (srvgg_model.cpp,
+// srvgg.hip; RestorationPipeline._sr_realesrgan, src/inference.py:579-591; the net, :335-336)
+int irx_srvgg_workspace_bytes(const irx_model* m, int B, int H, int W, size_t* bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(bytes, "null argument");
+  *bytes = const_cast<Srvgg*>(as<Srvgg>(m, IRX_MODEL_SRVGG))->workspace_bytes(B, H, W);
+  IRX_API_END
+}
+int irx_srvgg_u8(irx_model* m, void* s, const uint8_t* in_u8, int B, int H, int W, const float* in_lut,
+                 uint8_t* out_u8, float* out_f, void* ws, size_t ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(in_u8 && in_lut && out_u8 && ws, "null image, table, output or workspace pointer");
+  IRX_CHECK(B > 0 && H >= 1 && W >= 1, "SRVGG: batch, H and W must be positive");
+  as<Srvgg>(m, IRX_MODEL_SRVGG)->enhance(S(s), in_u8, B, H, W, in_lut, out_u8, out_f, (char*)ws, ws_bytes);
+  IRX_API_END
+}
+static void srvgg_op_shape(int B, int H, int W) {
+  IRX_CHECK(B > 0 && H > 0 && W > 0, "batch and sizes must be positive");
+  IRX_CHECK((long)B * H * W * 64 <= 0x7fffffffL, "batch x image too large for one call");
+}
+int irx_op_srvgg_conv(void* s, const void* x, int B, int H, int W, const void* w, const float* bias,
+                      const float* slope, void* out) {
+  IRX_API_BEGIN
+  srvgg_op_shape(B, H, W);
+  srvgg_conv(x, B, H, W, w, bias, slope, out, S(s));
+  IRX_API_END
+}
+int irx_op_srvgg_tail(void* s, const void* x, const uint8_t* in_u8, int B, int H, int W, const float* in_lut,
+                      const void* w, const float* bias, uint8_t* out_u8, float* out_f) {
+  IRX_API_BEGIN
+  srvgg_op_shape(B, H, W);
+  srvgg_tail(x, in_u8, B, H, W, in_lut, w, bias, out_u8, out_f, S(s));
+  IRX_API_END
+}
+int irx_op_srvgg_prelu(void* s, int dtype, const void* x, long rows, int C, const float* slope, void* out) {
+  IRX_API_BEGIN
+  srvgg_prelu(dtype, x, rows, C, slope, out, S(s));
   IRX_API_END
 }
 // ------------------------------------------------------------------ single ops

@@ -1,4 +1,5 @@
-// irx — native model graphs (UNet2DConditionModel, AutoencoderKL, CLIPTextModel, LPIPS AlexNet, FID InceptionV3) over the irx kernels.
+// irx — native model graphs (UNet2DConditionModel, AutoencoderKL, CLIPTextModel, LPIPS AlexNet, FID InceptionV3,
+// Real-ESRGAN SRVGGNetCompact) over the irx kernels.
 #pragma once
 #include <map>
 #include <memory>
@@ -286,6 +287,26 @@ class InceptionFid : public Model {
   Act block_e(Ctx& c, Act& x, int& u);
   void run(Ctx& c, const float* x, int B, int H, int W, float* out);
   std::vector<Unit> units_;
+};
+
+// Real-ESRGAN's SRVGGNetCompact(3, 3, num_feat=64, num_conv=32, upscale=4, act_type='prelu') (srvgg_host.py; the
+// reference's src/inference.py:335-336, :579-591): uint8 RGB in, uint8 RGB x4 out.  fp16 is the product (the fused
+// kernels of srvgg.hip, or conv2d + PReLU with srvgg_fused = 0), fp32 the parity engine on gemm()'s exact-f32 path;
+// bf16 is refused.  The config is not read.
+class Srvgg : public Model {
+ public:
+  Srvgg(const irx_model_config& cfg, int dtype);
+  static constexpr int kConvs = 34, kFeat = 64, kOut = 48;
+  size_t workspace_bytes(int B, int H, int W);
+  // img uint8 [B][H][W][3]; lut float[256] (srvgg_host.input_table); out_u8 [B][4H][4W][3]; out_f the same shape
+  // (the unclamped result, fp32) or null
+  void enhance(hipStream_t s, const uint8_t* img, int B, int H, int W, const float* lut, uint8_t* out_u8,
+               float* out_f, char* ws, size_t cap);
+
+ private:
+  void run(Ctx& c, const uint8_t* img, int B, int H, int W, const float* lut, uint8_t* out_u8, float* out_f);
+  P cw_[kConvs], cb_[kConvs], sl_[kConvs - 1];
+  int cin0_ = 4;
 };
 
 }  // namespace irx

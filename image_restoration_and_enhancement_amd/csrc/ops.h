@@ -396,4 +396,25 @@ void fid_maxpool3s2(const float* x, int N, int H, int W, int C, float* y, int ld
 // mean over the hw pixels of x fp32 [B][hw][C] -> y [B][C]: pixel order, one division
 void fid_gap(const float* x, int B, int hw, int C, float* y, hipStream_t s);
 
+// ------------------------------------------------------------ Real-ESRGAN SRVGGNetCompact (srvgg.hip; Srvgg, models.h)
+extern int g_srvgg_fused;    // 1: the fp16 engine runs the fused head / body / tail kernels (0: conv2d + PReLU, A/B)
+extern int g_srvgg_blocks;   // persistent blocks of the body / tail grid (0: one per CU)
+// fp16 engine.  x / y fp16 NHWC [B][H][W][64]; w fp16 [Cout][3][3][Cin]; bias / slope fp32, rounded to fp16 on read
+// head: uint8 [B][H][W][3] -> lut float[256] -> fp16 -> conv 3 -> 64 (w's Cin padded to cp) + bias + PReLU
+void srvgg_head(const uint8_t* img, int B, int H, int W, const float* lut, const void* w, int cp, const float* bias,
+                const float* slope, void* y, hipStream_t s);
+// a body layer: conv 64 -> 64 + bias + PReLU; x != y
+void srvgg_conv(const void* x, int B, int H, int W, const void* w, const float* bias, const float* slope, void* y,
+                hipStream_t s);
+// the tail: conv 64 -> 48 + bias, pixel shuffle 4, + the input pixel, clamp, * 255, rint -> out_u8 [B][4H][4W][3];
+// out_f (or null): the unclamped fp32 value of the same fp16 result
+void srvgg_tail(const void* x, const uint8_t* img, int B, int H, int W, const float* lut, const void* w,
+                const float* bias, uint8_t* out_u8, float* out_f, hipStream_t s);
+// the glue of the conv2d graph (dtype F32 or F16): uint8 -> lut -> NHWC with channels zero padded to 16 bytes;
+// per-channel PReLU of [rows][C] (x == y allowed); the tail's epilogue on a stored [B][H][W][48] conv output
+void srvgg_input(int dtype, const uint8_t* img, long npix, const float* lut, void* out, hipStream_t s);
+void srvgg_prelu(int dtype, const void* x, long rows, int C, const float* slope, void* y, hipStream_t s);
+void srvgg_shuffle_add(int dtype, const void* conv, const uint8_t* img, int B, int H, int W, const float* lut,
+                       uint8_t* out_u8, float* out_f, hipStream_t s);
+
 }  // namespace irx

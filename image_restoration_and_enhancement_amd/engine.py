@@ -34,7 +34,7 @@ def dtype_code(dtype) -> int:
 
 def model_config(kind: int, cfg) -> L.ModelConfig:
     c = L.ModelConfig()
-    if kind in (L.IRX_MODEL_LPIPS, L.IRX_MODEL_FID):       # fixed architecture: the native model does not read the config
+    if kind in (L.IRX_MODEL_LPIPS, L.IRX_MODEL_FID, L.IRX_MODEL_SRVGG):       # fixed architecture: the native model does not read the config
         return c
     if kind == L.IRX_MODEL_UNET:
         assert isinstance(cfg, UNetConfig)

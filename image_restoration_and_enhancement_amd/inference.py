@@ -26,10 +26,15 @@ Differences that follow from the engine (documented in INTEGRATION.md):
   (`fine_tuned_dir == "nonexistent"`), from a local Hugging Face cache snapshot of `pretrained_id` (no
   network).  `config[task]["weights"] = "random"` selects seeded random weights (benchmarks / tests).
 * tasks that resolve to the same weights (denoise / sr / colorize in pretrained mode) share one engine.
+* Real-ESRGAN (`default_backend` "realesrgan", or "auto" after a failed SD load) runs the compact network the
+  reference constructs (src/inference.py:335-336) from a weight file the user names: `config["sr"]
+  ["realesrgan_weights"]` or the environment variable IRX_REALESRGAN_WEIGHTS (a file, or a directory holding one
+  `*.pth` / `*.safetensors`).  Nothing is downloaded; with nothing configured the backend behaves as before.
 """
 from __future__ import annotations
 
 import logging
+import os
 from pathlib import Path
 from typing import Any, Dict, List, Literal, Optional, Sequence
 
@@ -73,6 +78,33 @@ class NativeSDModel:
 
     def __repr__(self):
         return f"NativeSDModel({self.kind}, {self.source})"
+
+
+class RealESRGANModel:
+    """What `models["sr"]` holds when Real-ESRGAN serves super-resolution: an object with an `enhance` method, which
+    is what the reference dispatches on (`hasattr(model, 'enhance')`, src/inference.py:538).  On a ROCm device it wraps
+    `srvgg_gpu.RealESRGANCompact` in fp16 (the reference's `half=self.device == "cuda"`), on the CPU
+    `srvgg_host.enhance` in fp32."""
+
+    def __init__(self, weights, device: str, source: str):
+        self.device = device
+        self.source = source
+        self.net = None
+        self.weights = weights
+        if str(device).startswith("cuda"):
+            from . import srvgg_gpu
+            self.net = srvgg_gpu.RealESRGANCompact(weights, device, "fp16")
+
+    def enhance(self, images: np.ndarray) -> np.ndarray:
+        """uint8 RGB [H, W, 3] or [B, H, W, 3] -> the uint8 x4 result (numpy)."""
+        if self.net is not None:
+            return self.net.enhance(np.ascontiguousarray(images)).cpu().numpy()
+        from . import srvgg_host
+        out = srvgg_host.enhance(np.ascontiguousarray(images), self.weights, torch.float32, half=False)
+        return out if isinstance(out, np.ndarray) else out.numpy()
+
+    def __repr__(self):
+        return f"RealESRGANModel({self.source})"
 
 
 def _resolve_pretrained(repo_id: str) -> Path:
@@ -200,8 +232,24 @@ class RestorationPipeline:
                 if backend == "sd_img2img":
                     raise RuntimeError(f"Stable Diffusion Img2Img failed: {e}")
                 logger.warning(f"Stable Diffusion Img2Img failed: {e}")
-        if backend == "realesrgan":
-            raise ImportError("Real-ESRGAN is not available (its weights are a network download)")
+        if backend in ("auto", "realesrgan"):
+            src = self.config["sr"].get("realesrgan_weights") or os.environ.get("IRX_REALESRGAN_WEIGHTS")
+            if src:
+                try:
+                    from . import srvgg_host
+                    self.models["sr"] = RealESRGANModel(srvgg_host.load_weights(src), self.device, str(src))
+                    logger.info(f"Super-resolution model ready (Real-ESRGAN, {src})")
+                    return
+                except IrxError:
+                    raise
+                except Exception as e:
+                    if backend == "realesrgan":
+                        raise RuntimeError(f"Real-ESRGAN loading failed: {e}")
+                    logger.warning(f"Real-ESRGAN loading failed: {e}")
+                    logger.info("Using LANCZOS upscaling")
+            elif backend == "realesrgan":
+                raise ImportError("Real-ESRGAN is not available (its weights are a network download; name a local "
+                                  "file in config['sr']['realesrgan_weights'] or IRX_REALESRGAN_WEIGHTS)")
         if backend in ("auto", "lanczos", "realesrgan"):
             self.models["sr"] = "lanczos"
             logger.info("Super-resolution model ready (LANCZOS fallback)")
@@ -284,6 +332,8 @@ class RestorationPipeline:
         model = self.models["sr"]
         if isinstance(model, NativeSDModel):
             return self._sr_sd(image, model, scale=scale, **kwargs)
+        if hasattr(model, "enhance"):
+            return self._sr_realesrgan(image, model, scale=scale)
         return self._sr_lanczos(image, scale=scale)
 
     @staticmethod
@@ -311,12 +361,54 @@ class RestorationPipeline:
             logger.warning(f"Stable Diffusion upscaling failed: {e}, falling back to LANCZOS")
             return self._sr_lanczos(image, scale=scale)
 
+    def _sr_realesrgan(self, image: Image.Image, model, scale: int) -> Image.Image:
+        """`model.enhance(img, outscale=scale)` (src/inference.py:579-591).  The net is x4; for another scale the
+        reference resizes the x4 result with cv2.INTER_LANCZOS4, here Pillow's LANCZOS (deviations)."""
+        try:
+            w, h = image.size
+            out = Image.fromarray(model.enhance(np.array(image.convert("RGB"))))
+            if scale != 4:
+                size = (w * scale, h * scale)
+                if self.device.startswith("cuda"):
+                    from . import resample
+                    out = resample.resize_pil(out, size, Image.LANCZOS, self.device)
+                else:
+                    out = out.resize(size, Image.LANCZOS)
+            return out
+        except IrxError:
+            raise
+        except Exception as e:
+            logger.warning(f"Real-ESRGAN upscaling failed: {e}, falling back to LANCZOS")
+            return self._sr_lanczos(image, scale=scale)
+
     def _sr_lanczos(self, image: Image.Image, scale: int) -> Image.Image:
         if self.device.startswith("cuda"):         # the same PIL LANCZOS resize, on the GPU (same bytes)
             from . import resample
             w, h = image.size
             return resample.resize_pil(image, (w * scale, h * scale), Image.LANCZOS, self.device)
         return classical.sr_lanczos(image, scale)
+
+    def _sr_realesrgan_batch(self, model, images: List[Image.Image], max_batch: int) -> List[Image.Image]:
+        """Equal-size images as one `enhance` call of up to `max_batch`; each image gets its single call's bytes (the
+        network's result does not depend on the batch: tests/test_srvgg_gpu.py)."""
+        out: List[Optional[Image.Image]] = [None] * len(images)
+        groups: Dict[tuple, List[int]] = {}
+        for i, im in enumerate(images):
+            groups.setdefault(im.size, []).append(i)
+        for idx in groups.values():
+            for k in range(0, len(idx), max_batch):
+                chunk = idx[k:k + max_batch]
+                try:
+                    res = model.enhance(np.stack([np.array(images[i].convert("RGB")) for i in chunk]))
+                    res = [Image.fromarray(r) for r in res]
+                except IrxError:
+                    raise
+                except Exception as e:
+                    logger.warning(f"batched Real-ESRGAN failed ({e}); running the single-image entry point per image")
+                    res = [self.super_resolve(images[i]) for i in chunk]
+                for i, r in zip(chunk, res):
+                    out[i] = r
+        return out  # type: ignore[return-value]
 
     # ------------------------------------------------------------------------------------ colorize
     @staticmethod
@@ -475,6 +567,8 @@ class RestorationPipeline:
                   "colorize": lambda im, mk: self.colorize(im, **pk),
                   "inpaint": lambda im, mk: self.inpaint(im, mask=mk, **pk)}[task]
         masks = list(masks) if masks is not None else [None] * len(images)
+        if task == "sr" and isinstance(model, RealESRGANModel):
+            return self._sr_realesrgan_batch(model, list(images), max_batch)
         if not isinstance(model, NativeSDModel):
             return [single(im, mk) for im, mk in zip(images, masks)]
         out: List[Optional[Image.Image]] = [None] * len(images)

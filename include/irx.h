@@ -31,6 +31,9 @@ extern "C" {
 #define IRX_MODEL_CLIP 2
 #define IRX_MODEL_LPIPS 3   /* LPIPS(alex) v0.1 (src/metrics.py:97-111): fp32 only, the config is not read */
 #define IRX_MODEL_FID 4     /* InceptionV3 pooled features (src/metrics.py:70-80): fp32 only, the config is not read */
+/* Real-ESRGAN's SRVGGNetCompact(3, 3, 64, 32, upscale 4, prelu) (src/inference.py:335-336): IRX_F16 (the product, the
+ * reference's half on a GPU) or IRX_F32 (parity); IRX_BF16 is refused at creation; the config is not read */
+#define IRX_MODEL_SRVGG 5
 
 /* weight layouts of manifest entries (how the host packs diffusers tensors into the blob) */
 #define IRX_LAYOUT_VEC 0   /* [n] fp32, zero padded                                  */
@@ -373,6 +376,37 @@ int irx_op_fid_bn_relu(void* stream, const float* x, long rows, int C, const flo
 int irx_op_fid_avgpool3(void* stream, const float* x, int n, int H, int W, int C, float* out);
 int irx_op_fid_maxpool3s2(void* stream, const float* x, int n, int H, int W, int C, float* out, int ldo, int coff);
 int irx_op_fid_gap(void* stream, const float* x, int batch, int hw, int C, float* out);
+
+/* ---- Real-ESRGAN, the compact network (RestorationPipeline._sr_realesrgan, src/inference.py:579-591: model.enhance
+ * at outscale 4; the net it constructs, :335-336; half = (device == "cuda"), :338-346) ----
+ * m is an IRX_MODEL_SRVGG model whose blob holds `body.{0,2,..,66}.{weight,bias}` (convs [64,3,3,3], 32 x [64,64,3,3],
+ * [48,64,3,3]) and `body.{1,3,..,65}.weight` (PReLU slopes [64]), the keys of realesr-general-x4v3.pth.
+ * in_u8 [batch][H][W][3] RGB in device memory, H, W >= 1; in_lut = device float[256], float32(v) / 255
+ * (srvgg_host.input_table); out_u8 [batch][4H][4W][3] = round_half_even(clamp(net(x), 0, 1) * 255) with
+ * net(x) = pixel_shuffle(body(x), 4) + nearest_x4(x); out_f (NULL: not wanted) fp32 of the same shape = net(x) before
+ * the clamp.  An IRX_F16 model rounds to fp16 after each conv + bias, each PReLU and the final add, accumulating in
+ * fp32 (the fused kernels of srvgg.hip; option srvgg_fused = 0: the same graph on the general conv kernels); an IRX_F32
+ * model runs every conv in exact fp32.  The same bits on every run and at every batch position.
+ * ws: irx_srvgg_workspace_bytes(m, batch, H, W) bytes of device memory, 16-byte aligned (it depends on srvgg_fused).
+ * The kernels index with 64-bit offsets, but the general conv kernels count rows in an int, so batch * H * W * 64 >
+ * INT_MAX is refused for both engines.  A refused argument (null pointer, batch <= 0, H or W < 1, that size limit, a
+ * model of another kind or without a bound blob, a short workspace) is a status and launches nothing.  Enqueues on
+ * `stream`: no allocation, no synchronisation. */
+int irx_srvgg_workspace_bytes(const irx_model* m, int batch, int H, int W, size_t* bytes);
+int irx_srvgg_u8(irx_model* m, void* stream, const uint8_t* in_u8, int batch, int H, int W, const float* in_lut,
+                 uint8_t* out_u8, float* out_f, void* ws, size_t ws_bytes);
+/* the kernels of the network on their own (tests).  x / out: fp16 NHWC [batch][H][W][64], x != out; weight fp16
+ * [Cout][3][3][64]; bias and slope fp32, rounded to fp16 when read.
+ * irx_op_srvgg_conv: one body layer, out = prelu(fp16(conv3x3(x) + bias)) (srvgg_arch.py: conv, then PReLU).
+ * irx_op_srvgg_tail: the last conv (Cout 48) + bias, pixel shuffle 4, + the input pixel from in_u8 / in_lut, as
+ *   irx_srvgg_u8 finishes: out_u8 [batch][4H][4W][3], out_f the same shape or NULL.
+ * irx_op_srvgg_prelu: out[r][c] = x[r][c] > 0 ? x[r][c] : slope[c] * x[r][c] over [rows][C] of dtype IRX_F32 or
+ *   IRX_F16 (slope and product rounded to fp16), C a multiple of 16 bytes of elements; x == out is allowed. */
+int irx_op_srvgg_conv(void* stream, const void* x, int batch, int H, int W, const void* weight, const float* bias,
+                      const float* slope, void* out);
+int irx_op_srvgg_tail(void* stream, const void* x, const uint8_t* in_u8, int batch, int H, int W, const float* in_lut,
+                      const void* weight, const float* bias, uint8_t* out_u8, float* out_f);
+int irx_op_srvgg_prelu(void* stream, int dtype, const void* x, long rows, int C, const float* slope, void* out);
 
 /* ---- multi-GPU: RCCL over xGMI (SURVEY.md §8b `irx_weights_bcast(handle, rcclComm)`, §8e) ----
    The reference has no multi-device path (src/inference.py:52-57 picks one device; it stands in for
