@@ -191,9 +191,20 @@ _SIGS = {
     "irx_op_group_norm_parts": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, i32, vp, i32,
                                       vp]),
     "irx_op_group_norm_parts_ab": (i32, [vp, i32, i32, i32, i32, f32, vp, vp, vp, i32, vp, vp]),
+    "irx_op_softmax_rows": (i32, [vp, i32, vp, i64, i32, i32, vp, i64]),
+    "irx_op_transpose2d": (i32, [vp, i32, vp, i64, i32, i32, vp, i64, i32, i64, i64]),
+    "irx_op_timestep_embed": (i32, [vp, i32, vp, i32, i32, i32, f32, vp]),
+    "irx_op_embed_tokens": (i32, [vp, i32, vp, i32, i32, vp, vp, i32, vp]),
 }
 
 EXPORTED = tuple(_SIGS)
+
+# plan queries for tests and scripts: exported by the library, not declared in include/irx.h (so not in EXPORTED)
+_DEBUG_SIGS = {
+    "irx_debug_gemm_tile": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
+    "irx_debug_conv_plan": (i32, [i32] * 17 + [C.POINTER(i32)]),
+}
+_SIGS.update(_DEBUG_SIGS)
 
 _lib = None
 

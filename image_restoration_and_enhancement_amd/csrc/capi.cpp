@@ -867,6 +867,39 @@ int irx_debug_gemm_tile(int dtype, int M, int N, int K, int geglu, int imgs, int
   IRX_API_END
 }
 
+// (tests; not part of irx.h) the plan of the convolution irx_op_conv2d would run for this geometry under the current
+// options: plan = {path (GemmPath), BM, BN, group_m, splits, tiles_m, tiles_n}; BM / BN / tiles are zeros when the
+// 4-wave or the streaming kernel runs the call
+int irx_debug_conv_plan(int dtype, int c0, int c1, int n, int hin, int win, int hv, int wv, int cout, int kh, int kw,
+                        int stride, int pad_t, int pad_l, int ho, int wo, int out_f32, int* plan) {
+  IRX_API_BEGIN
+  IRX_CHECK(plan, "null argument");
+  GemmArgs a;
+  a.dtype = dtype;
+  a.conv = 1;
+  a.g.src0 = (const void*)(uintptr_t)4096;   // (aligned stand-ins, never read)
+  a.g.src1 = c1 ? (const void*)(uintptr_t)4096 : nullptr;
+  a.g.C0 = c0; a.g.C1 = c1;
+  a.g.N = n; a.g.Hin = hin; a.g.Win = win; a.g.Hv = hv; a.g.Wv = wv;
+  a.g.KH = kh; a.g.KW = kw; a.g.stride = stride; a.g.pad_t = pad_t; a.g.pad_l = pad_l; a.g.Ho = ho; a.g.Wo = wo;
+  a.M = n * ho * wo; a.N = cout; a.K = kh * kw * (c0 + c1);
+  a.B = (const void*)(uintptr_t)4096; a.ldb = a.K;
+  a.C = (void*)(uintptr_t)4096; a.ldc = cout; a.out_f32 = out_f32;
+  a.rows_per_group = ho * wo;
+  a.ldr = cout;
+  a.imgs = n;
+  conv1x1_as_dense(a);   // as irx_op_conv2d does
+  const GemmPlan p = gemm_plan(a);
+  plan[0] = p.path;
+  plan[1] = p.large() ? p.BM : 0;
+  plan[2] = p.large() ? p.BN : 0;
+  plan[3] = p.large() ? p.group_m : 0;
+  plan[4] = p.large() ? p.splits : 1;
+  plan[5] = p.large() ? (a.M + p.BM - 1) / p.BM : 0;
+  plan[6] = p.large() ? (a.N + p.BN - 1) / p.BN : 0;
+  IRX_API_END
+}
+
 int irx_op_group_norm(void* s, int dtype, const void* x0, const void* x1, int c0, int c1, int n, int hw, int groups,
                       float eps, const float* gamma, const float* beta, int silu, void* out, void* ws) {
   IRX_API_BEGIN
@@ -1199,6 +1232,42 @@ int irx_op_geglu(void* s, int dtype, const void* proj, int M, int F, void* out) 
   IRX_API_BEGIN
   IRX_CHECK(proj && out, "null buffer");
   geglu(dtype, proj, 2L * F, M, F, out, F, 0, S(s));
+  IRX_API_END
+}
+
+// ---- the elementwise kernels the models call between GEMMs, one entry each (tests)
+int irx_op_softmax_rows(void* s, int dtype, const float* in, long ldi, int rows, int cols, void* out, long ldo) {
+  IRX_API_BEGIN
+  IRX_CHECK(in && out, "null buffer");
+  IRX_CHECK(rows > 0 && cols > 0 && ldi >= cols && ldo >= cols, "softmax_rows shape");
+  softmax_rows(dtype, in, ldi, rows, cols, out, ldo, S(s));
+  IRX_API_END
+}
+
+int irx_op_transpose2d(void* s, int dtype, const void* in, long ldi, int rows, int cols, void* out, long ldo,
+                       int batch, long s_in, long s_out) {
+  IRX_API_BEGIN
+  IRX_CHECK(in && out, "null buffer");
+  IRX_CHECK(rows > 0 && cols > 0 && batch > 0 && ldi >= cols && ldo >= rows, "transpose2d shape");
+  transpose2d(dtype, in, ldi, rows, cols, out, ldo, batch, s_in, s_out, S(s));
+  IRX_API_END
+}
+
+int irx_op_timestep_embed(void* s, int dtype, const float* t, int B, int dim, int flip_sin_to_cos, float shift,
+                          void* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(t && out, "null buffer");
+  IRX_CHECK(B > 0 && dim > 0 && dim % 2 == 0, "timestep_embed shape");
+  timestep_embed(dtype, t, B, dim, flip_sin_to_cos, shift, out, S(s));
+  IRX_API_END
+}
+
+int irx_op_embed_tokens(void* s, int dtype, const int* ids, int B, int L, const void* tok, const void* pos, int D,
+                        void* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(ids && tok && pos && out, "null buffer");
+  IRX_CHECK(B > 0 && L > 0 && D > 0, "embed_tokens shape");
+  embed_tokens(dtype, ids, B, L, tok, pos, D, out, S(s));
   IRX_API_END
 }
 

@@ -538,6 +538,19 @@ int irx_op_group_norm_parts(void* stream, int dtype, const void* x0, const void*
    NULL); both pairs of floats */
 int irx_op_group_norm_parts_ab(void* stream, int c0, int n, int hw, int groups, float eps, const float* gamma,
                                const float* beta, const double* p0, int r0, void* ab, void* mr);
+/* The elementwise kernels the models run between GEMMs, one entry each.
+   softmax_rows: out[r][0, cols) = softmax(in[r][0, cols)) of fp32 rows (row strides ldi, ldo); it also ZEROES the
+   padded columns [cols, ldo) of every output row (the fp32 VAE attention multiplies them with V^T's padding).
+   transpose2d: out[z][c][r] = in[z][r][c] per batch z (strides s_in, s_out); columns [rows, ldo) of out are left alone.
+   timestep_embed: out[b][dim] = the sinusoidal embedding of t[b] (diffusers get_timestep_embedding, max_period 1e4).
+   embed_tokens: out[b][l][:] = tok[ids[b][l]][:] + pos[l][:], summed in fp32. */
+int irx_op_softmax_rows(void* stream, int dtype, const float* in, long ldi, int rows, int cols, void* out, long ldo);
+int irx_op_transpose2d(void* stream, int dtype, const void* in, long ldi, int rows, int cols, void* out, long ldo,
+                       int batch, long s_in, long s_out);
+int irx_op_timestep_embed(void* stream, int dtype, const float* t, int B, int dim, int flip_sin_to_cos, float shift,
+                          void* out);
+int irx_op_embed_tokens(void* stream, int dtype, const int* ids, int B, int L, const void* tok, const void* pos, int D,
+                        void* out);
 
 #ifdef __cplusplus
 }

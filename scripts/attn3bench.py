@@ -13,6 +13,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from image_restoration_and_enhancement_amd import _lib as L  # noqa: E402
 from tests import opref as O  # noqa: E402
 
+O.G.ENABLED = False   # timing: plain buffers, none of the tests' guard bands, operand copies or syncs
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--rounds", type=int, default=3)

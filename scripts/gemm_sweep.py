@@ -14,6 +14,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from image_restoration_and_enhancement_amd import _lib as L  # noqa: E402
 from tests import opref as O  # noqa: E402
 
+O.G.ENABLED = False   # timing: plain buffers, none of the tests' guard bands, operand copies or syncs
+
 B = 16
 UNET_CONV = [  # (count per eval, N, H, W, C0, C1, Cout, k, stride, up)
     (4, B, 64, 64, 320, 0, 320, 3, 1, None), (1, B, 64, 64, 320, 0, 320, 3, 2, None),

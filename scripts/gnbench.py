@@ -11,6 +11,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from image_restoration_and_enhancement_amd import _lib as L  # noqa: E402
 from tests import opref as O  # noqa: E402
 
+O.G.ENABLED = False   # timing: plain buffers, none of the tests' guard bands, operand copies or syncs
+
 SHAPES = [(16, 64, 64, 320, 0), (16, 32, 32, 640, 0), (16, 16, 16, 1280, 0), (16, 8, 8, 2560, 0),
           (16, 8, 8, 1280, 1280), (16, 64, 64, 320, 320), (8, 512, 512, 128, 0), (8, 256, 256, 256, 0)]
 ap = argparse.ArgumentParser()

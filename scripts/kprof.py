@@ -26,6 +26,8 @@ from image_restoration_and_enhancement_amd import _lib as L  # noqa: E402
 from image_restoration_and_enhancement_amd.engine import geglu64_order  # noqa: E402
 from tests import opref as O  # noqa: E402
 
+O.G.ENABLED = False   # timing: plain buffers, none of the tests' guard bands, operand copies or syncs
+
 
 def main():
     ap = argparse.ArgumentParser()

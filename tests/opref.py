@@ -1,5 +1,9 @@
 """Thin torch wrappers over the single-op C ABI (irx_op_*) used by the GPU parity tests,
-plus the fp32 PyTorch-CPU reference of each op."""
+plus the fp32 PyTorch-CPU reference of each op.
+
+Every wrapper runs its kernel on guarded buffers (tests/guard.py): the output is NaN-poisoned between sentinel bands
+and checked before it is returned, every floating-point operand is a copy followed by a NaN tail, and every workspace
+starts as 0xFF bytes."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from image_restoration_and_enhancement_amd import _lib as L
+from tests import guard as G
 
 DT = {torch.float32: L.IRX_F32, torch.bfloat16: L.IRX_BF16, torch.float16: L.IRX_F16}
 
@@ -37,47 +42,49 @@ def conv2d(x0, w_oihw, bias, stride=1, pad=(1, 1), out_hw=None, x1=None, up_hw=N
         Wo = (wv + 2 * pad[1] - KW) // stride + 1
     else:
         Ho, Wo = out_hw
-    out = torch.empty((N, Ho, Wo, Co), dtype=torch.float32 if out_f32 else dt, device=x0.device)
-    b = bias.float().to(x0.device).contiguous() if bias is not None else None
+    out = G.out(x0.device, torch.float32 if out_f32 else dt, N, Ho, Wo, Co)
+    b = G.inp(bias.float().to(x0.device).contiguous()) if bias is not None else None
+    x0, x1, wk, rowadd, residual = (G.inp(t) for t in (x0, x1, wk, rowadd, residual))
     L.call("irx_op_conv2d", S(), DT[dt], P(x0), P(x1), C0, C1, N, H, W, hv, wv, P(wk), P(b), Co, KH, KW, stride,
-           pad[0], pad[1], Ho, Wo, P(rowadd), rowadd.shape[1] if rowadd is not None else 0, P(residual), P(out),
+           pad[0], pad[1], Ho, Wo, P(rowadd), rowadd.shape[1] if rowadd is not None else 0, P(residual), out.ptr(),
            int(out_f32), act)
-    return out
+    return G.done(out, (N, Ho, Wo, Co), "irx_op_conv2d")
 
 
-def gemm(A, Bw, bias=None, alpha=1.0, act=0, residual=None, out_f32=False, batch=1, guard_rows=0):
-    """A [M,K] (or [b,M,K]), Bw [N,K] (or [b,N,K]) device tensors -> [M,N].  guard_rows > 0: the output is the head
-    of a larger buffer whose trailing rows hold a sentinel, asserted untouched after the call (no write past M)."""
+def gemm(A, Bw, bias=None, alpha=1.0, act=0, residual=None, out_f32=False, batch=1, guard_rows=0, ld_pad=0):
+    """A [M,K] (or [b,M,K]), Bw [N,K] (or [b,N,K]) device tensors -> [M,N] (or [b,M,N]).  The output's row stride is
+    ldc = N + ld_pad (the pad columns are sentinels: not the kernel's to write).  guard_rows is kept for its callers:
+    every output is followed by a full tile of sentinel rows now."""
     dt = A.dtype
+    odt = torch.float32 if out_f32 else dt
+    assert ld_pad % 8 == 0
     if batch > 1:
         _, M, K = A.shape
         N = Bw.shape[1]
-        out = torch.empty((batch, M, N), dtype=torch.float32 if out_f32 else dt, device=A.device)
-        sA, sB, sC = M * K, N * K, M * N
+        ldc = N + ld_pad
+        out = G.Out(A.device, odt, M, N, ld=ldc, batch=batch)
+        sA, sB, sC, sR = M * K, N * K, M * ldc, M * N
     else:
         M, K = A.shape
         N = Bw.shape[0]
-        if guard_rows:
-            buf = torch.full((M + guard_rows, N), 1234.0, dtype=torch.float32 if out_f32 else dt, device=A.device)
-            L.call("irx_op_gemm", S(), DT[dt], M, N, K, P(A), K, P(Bw), K, P(buf), N, P(bias), float(alpha), act,
-                   P(residual), N, int(out_f32), 1, 0, 0, 0, 0)
-            assert bool((buf[M:] == 1234.0).all()), "GEMM wrote past its last output row"
-            return buf[:M]
-        out = torch.empty((M, N), dtype=torch.float32 if out_f32 else dt, device=A.device)
-        sA = sB = sC = 0
-    L.call("irx_op_gemm", S(), DT[dt], M, N, K, P(A), K, P(Bw), K, P(out), N, P(bias), float(alpha), act,
-           P(residual), N, int(out_f32), batch, sA, sB, sC, sC)
-    return out
+        ldc = N + ld_pad
+        out = G.Out(A.device, odt, M, N, ld=ldc)
+        sA = sB = sC = sR = 0
+    A, Bw, bias, residual = (G.inp(t) for t in (A, Bw, bias, residual))
+    L.call("irx_op_gemm", S(), DT[dt], M, N, K, P(A), K, P(Bw), K, out.ptr(), ldc, P(bias), float(alpha), act,
+           P(residual), N, int(out_f32), batch, sA, sB, sC, sR)
+    return out.check("irx_op_gemm")
 
 
 def group_norm(x0, gamma, beta, eps, groups=32, silu=False, x1=None):
     N, H, W, C0 = x0.shape
     C1 = x1.shape[3] if x1 is not None else 0
-    ws = torch.empty(L.load().irx_op_group_norm_ws_bytes(N, H * W, groups), dtype=torch.uint8, device=x0.device)
-    out = torch.empty((N, H, W, C0 + C1), dtype=x0.dtype, device=x0.device)
+    ws = G.ws(L.load().irx_op_group_norm_ws_bytes(N, H * W, groups), x0.device)
+    out = G.out(x0.device, x0.dtype, N, H, W, C0 + C1)
+    x0, x1, gamma, beta = (G.inp(t) for t in (x0, x1, gamma, beta))
     L.call("irx_op_group_norm", S(), DT[x0.dtype], P(x0), P(x1), C0, C1, N, H * W, groups, float(eps),
-           P(gamma), P(beta), int(silu), P(out), P(ws))
-    return out
+           P(gamma), P(beta), int(silu), out.ptr(), P(ws))
+    return G.done(out, (N, H, W, C0 + C1), "irx_op_group_norm")
 
 
 def gn_conv3(x0, gamma, beta, eps, w_oihw, bias, groups=32, silu=True, x1=None, rowadd=None, residual=None,
@@ -96,13 +103,14 @@ def gn_conv3(x0, gamma, beta, eps, w_oihw, bias, groups=32, silu=True, x1=None, 
     wk = w_oihw.permute(0, 2, 3, 1).contiguous().to(device=x0.device, dtype=x0.dtype)
     b = bias.float().to(x0.device).contiguous() if bias is not None else None
     nb = L.load().irx_op_gn_conv3_ws_bytes(N, H * W, groups, C0 + C1)
-    ws = torch.empty(nb, dtype=torch.uint8, device=x0.device)
-    out = torch.empty((N, H, W, Co), dtype=x0.dtype, device=x0.device)
+    ws = G.ws(nb, x0.device)
+    out = G.out(x0.device, x0.dtype, N, H, W, Co)
+    x0, x1, gamma, beta, wk, b, rowadd, residual = (G.inp(t) for t in (x0, x1, gamma, beta, wk, b, rowadd, residual))
     L.call("irx_op_gn_conv3", S(), DT[x0.dtype], P(x0), P(x1), C0, C1, N, H, W, groups, float(eps), P(gamma),
            P(beta), int(silu), P(wk), P(b), Co, P(rowadd), rowadd.shape[1] if rowadd is not None else 0,
-           P(residual), P(out), P(ws), ctypes.byref(fused))
+           P(residual), out.ptr(), P(ws), ctypes.byref(fused))
     assert fused.value == 1
-    return out
+    return G.done(out, (N, H, W, Co), "irx_op_gn_conv3")
 
 
 # ------------------------------------------------------------------ GroupNorm producer partials and their consumers
@@ -121,20 +129,21 @@ def conv2d_gn_parts(x0, w_oihw, bias, x1=None, rowadd=None, residual=None, out_f
     assert Ci == C0 + C1
     wk = w_oihw.permute(0, 2, 3, 1).contiguous().to(device=x0.device, dtype=dt)
     b = bias.float().to(x0.device).contiguous() if bias is not None else None
-    out = torch.empty((N, H, W, Co), dtype=torch.float32 if out_f32 else dt, device=x0.device)
+    out = G.out(x0.device, torch.float32 if out_f32 else dt, N, H, W, Co)
+    x0, x1, wk, b, rowadd, residual = (G.inp(t) for t in (x0, x1, wk, b, rowadd, residual))
     rows, splits, halo, wsb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
 
     def call(o, parts, ws):
         L.call("irx_op_conv2d_gn_parts", S(), DT[dt], P(x0), P(x1), C0, C1, N, H, W, H, W, P(wk), P(b), Co, KH, KW, 1,
-               pad, pad, H, W, P(rowadd), rowadd.shape[1] if rowadd is not None else 0, P(residual), P(o),
+               pad, pad, H, W, P(rowadd), rowadd.shape[1] if rowadd is not None else 0, P(residual), o,
                int(out_f32), 0, P(parts), P(ws), C.byref(rows), C.byref(splits), C.byref(halo), C.byref(wsb))
         return {"R": rows.value, "splits": splits.value, "halo": halo.value}
 
     q = call(None, None, None)
     parts = _nan_parts(N * H * W // (q["R"] or 64), Co, x0.device)
-    ws = torch.empty(max(16, wsb.value), dtype=torch.uint8, device=x0.device)
-    assert call(out, parts, ws) == q
-    return out, parts, q
+    ws = G.ws(wsb.value, x0.device)
+    assert call(out.ptr(), parts, ws) == q
+    return G.done(out, (N, H, W, Co), "irx_op_conv2d_gn_parts"), parts, q
 
 
 def gemm_gn_parts(A, Bw, bias, residual, imgs, out_f32=False):
@@ -143,49 +152,52 @@ def gemm_gn_parts(A, Bw, bias, residual, imgs, out_f32=False):
     M, K = A.shape
     N = Bw.shape[0]
     assert not out_f32     # (the models' linear takes out_f32, a GroupNorm never reads such an output)
-    out = torch.empty((M, N), dtype=dt, device=A.device)
+    out = G.out(A.device, dt, M, N)
+    A, Bw, bias, residual = (G.inp(t) for t in (A, Bw, bias, residual))
     rows, splits, wsb = C.c_int(), C.c_int(), C.c_size_t()
 
     def call(o, parts, ws):
-        L.call("irx_op_gemm_gn_parts", S(), DT[dt], M, N, K, P(A), P(Bw), P(bias), P(residual), imgs, P(o), P(parts),
+        L.call("irx_op_gemm_gn_parts", S(), DT[dt], M, N, K, P(A), P(Bw), P(bias), P(residual), imgs, o, P(parts),
                P(ws), C.byref(rows), C.byref(splits), C.byref(wsb))
         return {"R": rows.value, "splits": splits.value, "halo": 0}
 
     q = call(None, None, None)
     parts = _nan_parts(M // (q["R"] or 64), N, A.device)
-    ws = torch.empty(max(16, wsb.value), dtype=torch.uint8, device=A.device)
-    assert call(out, parts, ws) == q
-    return out, parts, q
+    ws = G.ws(wsb.value, A.device)
+    assert call(out.ptr(), parts, ws) == q
+    return G.done(out, (M, N), "irx_op_gemm_gn_parts"), parts, q
 
 
 def upsample_conv_gn_parts(x, w2, bias):
     """x [n][h][w][c], w2 [4 c][2][2][c] (engine.conv_up2, device, x's dtype) -> (out [n][2h][2w][c], parts
     [4 n h w / R][c][2], info) through irx_op_upsample_conv_gn_parts."""
     n, h, w, c = x.shape
-    out = torch.empty((n, 2 * h, 2 * w, c), dtype=x.dtype, device=x.device)
+    out = G.out(x.device, x.dtype, n, 2 * h, 2 * w, c)
+    x, w2, bias = (G.inp(t) for t in (x, w2, bias))
     ok, rows, wsb = C.c_int(), C.c_int(), C.c_size_t()
 
     def call(o, parts, ws):
-        L.call("irx_op_upsample_conv_gn_parts", S(), DT[x.dtype], P(x), n, h, w, c, P(w2), P(bias), P(o), P(parts),
+        L.call("irx_op_upsample_conv_gn_parts", S(), DT[x.dtype], P(x), n, h, w, c, P(w2), P(bias), o, P(parts),
                P(ws), C.byref(ok), C.byref(rows), C.byref(wsb))
         return {"up2": ok.value, "R": rows.value}
 
     q = call(None, None, None)
     parts = _nan_parts(4 * n * h * w // (q["R"] or 64), c, x.device)
-    ws = torch.empty(max(16, wsb.value), dtype=torch.uint8, device=x.device)
-    assert call(out, parts, ws) == q
-    return out, parts, q
+    ws = G.ws(wsb.value, x.device)
+    assert call(out.ptr(), parts, ws) == q
+    return G.done(out, (n, 2 * h, 2 * w, c), "irx_op_upsample_conv_gn_parts"), parts, q
 
 
 def group_norm_parts(x0, p0, r0, gamma, beta, eps, groups=32, silu=False, x1=None, p1=None, r1=0):
     """GroupNorm(+SiLU) of (x0 | x1) [N][HW][C] from the partials p0 / p1 (irx_op_group_norm_parts)."""
     N, HW, C0 = x0.shape
     C1 = x1.shape[2] if x1 is not None else 0
-    ws = torch.empty(L.load().irx_op_group_norm_ws_bytes(N, HW, groups), dtype=torch.uint8, device=x0.device)
-    out = torch.empty((N, HW, C0 + C1), dtype=x0.dtype, device=x0.device)
+    ws = G.ws(L.load().irx_op_group_norm_ws_bytes(N, HW, groups), x0.device)
+    out = G.out(x0.device, x0.dtype, N, HW, C0 + C1)
+    x0, x1, gamma, beta = (G.inp(t) for t in (x0, x1, gamma, beta))
     L.call("irx_op_group_norm_parts", S(), DT[x0.dtype], P(x0), P(x1), C0, C1, N, HW, groups, float(eps), P(gamma),
-           P(beta), int(silu), P(out), P(p0), r0, P(p1), r1, P(ws))
-    return out
+           P(beta), int(silu), out.ptr(), P(p0), r0, P(p1), r1, P(ws))
+    return G.done(out, (N, HW, C0 + C1), "irx_op_group_norm_parts")
 
 
 def group_norm_parts_ab(p0, r0, C0, N, HW, gamma, beta, eps, groups=32):
@@ -199,28 +211,129 @@ def group_norm_parts_ab(p0, r0, C0, N, HW, gamma, beta, eps, groups=32):
 
 def layer_norm(x, gamma, beta, eps):
     rows, Cc = x.shape
-    out = torch.empty_like(x)
-    L.call("irx_op_layer_norm", S(), DT[x.dtype], P(x), rows, Cc, float(eps), P(gamma), P(beta), P(out))
-    return out
+    out = G.out(x.device, x.dtype, rows, Cc)
+    x, gamma, beta = (G.inp(t) for t in (x, gamma, beta))
+    L.call("irx_op_layer_norm", S(), DT[x.dtype], P(x), rows, Cc, float(eps), P(gamma), P(beta), out.ptr())
+    return G.done(out, (rows, Cc), "irx_op_layer_norm")
 
 
-def attention(q, k, v, heads, causal=False):
-    """q [B,Lq,C], k/v [B,Lk,C] device tensors (possibly strided views with unit last stride)."""
+def attention(q, k, v, heads, causal=False, ld_pad=0):
+    """q [B,Lq,C], k/v [B,Lk,C] device tensors (possibly strided views with unit last stride) -> [B,Lq,C] of row
+    stride ldo = C + ld_pad (the pad columns are sentinels)."""
     B, Lq, Cq = q.shape
     Lk = k.shape[1]
     d = Cq // heads
-    o = torch.empty((B, Lq, Cq), dtype=q.dtype, device=q.device)
+    assert ld_pad % 8 == 0
+    ldo = Cq + ld_pad
+    o = G.Out(q.device, q.dtype, Lq, Cq, ld=ldo, batch=B)
+    q, k, v = (G.inp(t) for t in (q, k, v))
     L.call("irx_op_attention", S(), DT[q.dtype], B, heads, Lq, Lk, d, P(q), q.stride(1), q.stride(0), P(k),
-           k.stride(1), k.stride(0), P(v), v.stride(1), v.stride(0), P(o), Cq, Lq * Cq, 1.0 / math.sqrt(d),
+           k.stride(1), k.stride(0), P(v), v.stride(1), v.stride(0), o.ptr(), ldo, Lq * ldo, 1.0 / math.sqrt(d),
            int(causal))
-    return o
+    return o.check("irx_op_attention")
 
 
 def geglu(proj):
     M, F2 = proj.shape
-    out = torch.empty((M, F2 // 2), dtype=proj.dtype, device=proj.device)
-    L.call("irx_op_geglu", S(), DT[proj.dtype], P(proj), M, F2 // 2, P(out))
-    return out
+    out = G.out(proj.device, proj.dtype, M, F2 // 2)
+    proj = G.inp(proj)
+    L.call("irx_op_geglu", S(), DT[proj.dtype], P(proj), M, F2 // 2, out.ptr())
+    return G.done(out, (M, F2 // 2), "irx_op_geglu")
+
+
+def gemm_geglu(A, W, bias):
+    """A [M,K], W [N,K] and bias [N] in the GEGLU64 row order -> [M, N/2] (irx_op_gemm_geglu)."""
+    M, K = A.shape
+    N = W.shape[0]
+    out = G.out(A.device, A.dtype, M, N // 2)
+    A, W, bias = (G.inp(t) for t in (A, W, bias))
+    L.call("irx_op_gemm_geglu", S(), DT[A.dtype], M, N, K, P(A), P(W), P(bias), out.ptr())
+    return G.done(out, (M, N // 2), "irx_op_gemm_geglu")
+
+
+def gemm_ln_out(A, W, bias, R, final_rs=False, eps=1e-5):
+    """-> (C [M,N], LayerNorm partials [M][N / 320][2] fp32, NaN before the call) (irx_op_gemm_ln_out)."""
+    M, K = A.shape
+    N = W.shape[0]
+    out = G.out(A.device, A.dtype, M, N)
+    parts = G.out(A.device, torch.float32, M, N // 320 * 2)
+    A, W, bias, R = (G.inp(t) for t in (A, W, bias, R))
+    L.call("irx_op_gemm_ln_out", S(), DT[A.dtype], M, N, K, P(A), P(W), P(bias), P(R), out.ptr(), parts.ptr(),
+           int(final_rs), float(eps))
+    return G.done(out, (M, N), "irx_op_gemm_ln_out"), G.done(parts, (M, N // 320, 2), "irx_op_gemm_ln_out parts")
+
+
+def gemm_ln_fold(x, Wg, u, v, rs=None, parts=None, T=0, geglu=False):
+    """The folded-LayerNorm projection (irx_op_gemm_ln_fold) -> [M, N] or, with geglu, [M, N/2]."""
+    M, K = x.shape
+    N = Wg.shape[0]
+    No = N // 2 if geglu else N
+    out = G.out(x.device, x.dtype, M, No)
+    x, Wg, u, v, rs, parts = (G.inp(t) for t in (x, Wg, u, v, rs, parts))
+    L.call("irx_op_gemm_ln_fold", S(), DT[x.dtype], M, N, K, P(x), P(Wg), P(u), P(v), P(rs), P(parts), T, int(geglu),
+           out.ptr())
+    return G.done(out, (M, No), "irx_op_gemm_ln_fold")
+
+
+def attention_hm(q, k, v, scale=None):
+    """q [B,H,Lq,d], k/v [B,H,Lk,d] contiguous (heads laid out per batch) -> [B,H,Lq,d] (irx_op_attention_hm)."""
+    B, H, Lq, d = q.shape
+    Lk = k.shape[2]
+    out = G.out(q.device, q.dtype, B, H, Lq, d)
+    q, k, v = (G.inp(t.contiguous()) for t in (q, k, v))
+    L.call("irx_op_attention_hm", S(), DT[q.dtype], B, H, Lq, Lk, d, P(q), P(k), P(v), out.ptr(),
+           1.0 / math.sqrt(d) if scale is None else float(scale))
+    return G.done(out, (B, H, Lq, d), "irx_op_attention_hm")
+
+
+# ------------------------------------------------------------------ elementwise kernels between the GEMMs
+def softmax_rows(x, cols, ldo, dt):
+    """x: fp32 [rows][ldi] device tensor of which columns [0, cols) are the scores -> the whole [rows][ldo] output
+    (the kernel owns every column of it: softmax in [0, cols), zeros in [cols, ldo))."""
+    rows, ldi = x.shape
+    out = G.Out(x.device, dt, rows, ldo)
+    xg = G.inp(x[:, :cols])          # (the input's own pad columns are NaN in the copy: they are not read)
+    L.call("irx_op_softmax_rows", S(), DT[dt], P(xg), ldi, rows, cols, out.ptr(), ldo)
+    return out.check("irx_op_softmax_rows")
+
+
+def transpose2d(x, ldo):
+    """x [batch][rows][cols] (a strided view: row stride ldi, batch stride s_in) -> [batch][cols][rows] of row stride
+    ldo; the pad columns [rows, ldo) are sentinels (the kernel must leave them alone)."""
+    batch, rows, cols = x.shape
+    out = G.Out(x.device, x.dtype, cols, rows, ld=ldo, batch=batch)
+    xg = G.inp(x)
+    L.call("irx_op_transpose2d", S(), DT[x.dtype], P(xg), x.stride(1), rows, cols, out.ptr(), ldo, batch, x.stride(0),
+           cols * ldo)
+    return out.check("irx_op_transpose2d")
+
+
+def timestep_embed(t, dim, flip, shift, dt):
+    B = t.shape[0]
+    out = G.out(t.device, dt, B, dim)
+    tg = G.inp(t)
+    L.call("irx_op_timestep_embed", S(), DT[dt], P(tg), B, dim, int(flip), float(shift), out.ptr())
+    return G.done(out, (B, dim), "irx_op_timestep_embed")
+
+
+def embed_tokens(ids, tok, pos):
+    """ids int32 [B][L], tok [V][D], pos [L][D] -> [B][L][D]."""
+    B, Lt = ids.shape
+    D = tok.shape[1]
+    out = G.out(tok.device, tok.dtype, B, Lt, D)
+    tg, pg = G.inp(tok), G.inp(pos)
+    L.call("irx_op_embed_tokens", S(), DT[tok.dtype], P(ids), B, Lt, P(tg), P(pg), D, out.ptr())
+    return G.done(out, (B, Lt, D), "irx_op_embed_tokens")
+
+
+def ref_timestep_embed(t, dim, flip, shift):
+    """float64: diffusers' get_timestep_embedding (max_period 10000, scale 1), the exponent formed as there and in the
+    kernel: -ln(10000) k / (dim / 2 - shift)."""
+    half = dim // 2
+    e = -math.log(10000.0) * torch.arange(half, dtype=torch.float64) / (half - shift)
+    arg = t.double()[:, None] * torch.exp(e)[None]
+    s, c = torch.sin(arg), torch.cos(arg)
+    return torch.cat([c, s] if flip else [s, c], -1)
 
 
 # ------------------------------------------------------------------ references (fp32 CPU)

@@ -142,9 +142,7 @@ def test_pair_geglu(device, dt, N, K):
     b = _r(N, seed=22).to(device).contiguous()
 
     def fn():
-        out = torch.empty(M, N // 2, dtype=dt, device=device)
-        L.call("irx_op_gemm_geglu", O.S(), O.DT[dt], M, N, K, O.P(A), O.P(W), O.P(b), O.P(out))
-        return out
+        return O.gemm_geglu(A, W, b)
     check(run_modes(fn, dt, M, N, K, geglu=True))
 
 
@@ -156,10 +154,7 @@ def test_pair_ln_fold(device, dt, N, geglu, K):
     x, Wg, u, v, rs = _fold_operands(dt, device, M, N, K, geglu)
 
     def fn():
-        out = torch.empty(M, N // 2 if geglu else N, dtype=dt, device=device)
-        L.call("irx_op_gemm_ln_fold", O.S(), O.DT[dt], M, N, K, O.P(x), O.P(Wg), O.P(u), O.P(v), O.P(rs), None, 0,
-               int(geglu), O.P(out))
-        return out
+        return O.gemm_ln_fold(x, Wg, u, v, rs=rs, geglu=geglu)
     check(run_modes(fn, dt, M, N, K, geglu=geglu))
 
 

@@ -44,13 +44,7 @@ def _dev(x, dt, device):
 
 
 def produce(A, W, bias, R, dt, device, final_rs=False):
-    M, K = A.shape
-    N = W.shape[0]
-    C = torch.empty(M, N, dtype=dt, device=device)
-    parts = torch.full((M, N // 320, 2), float("nan"), dtype=torch.float32, device=device)
-    L.call("irx_op_gemm_ln_out", O.S(), O.DT[dt], M, N, K, O.P(A), O.P(W), O.P(bias), O.P(R), O.P(C), O.P(parts),
-           int(final_rs), 1e-5)
-    return C, parts
+    return O.gemm_ln_out(A, W, bias, R, final_rs=final_rs, eps=1e-5)
 
 
 def two_pass(x):   # fp64 (mean, M2) per 320-column group
@@ -94,12 +88,7 @@ def _fold(W, b, gamma, beta, dt, device, geglu):
 
 
 def fold_gemm(x, Wg, u, v, dt, device, rs=None, parts=None, T=0, geglu=False):
-    M, K = x.shape
-    N = Wg.shape[0]
-    out = torch.empty(M, N // 2 if geglu else N, dtype=dt, device=device)
-    L.call("irx_op_gemm_ln_fold", O.S(), O.DT[dt], M, N, K, O.P(x), O.P(Wg), O.P(u), O.P(v), O.P(rs), O.P(parts),
-           T, int(geglu), O.P(out))
-    return out
+    return O.gemm_ln_fold(x, Wg, u, v, rs=rs, parts=parts, T=T, geglu=geglu)
 
 
 @pytest.mark.parametrize("dt", DT16)

@@ -281,9 +281,8 @@ def test_gemm_geglu_fused(device, M, C, dt):
     Wt = _r(8 * C, C, seed=81, scale=1 / math.sqrt(C))
     bias = _r(8 * C, seed=82)
     perm = geglu64_order(8 * C)
-    out = torch.empty(M, 4 * C, dtype=dt, device=device)
     a_d, w_d, b_d = _dev(A, dt, device), _dev(Wt[perm], dt, device), bias[perm].to(device).contiguous()
-    L.call("irx_op_gemm_geglu", O.S(), O.DT[dt], M, 8 * C, C, O.P(a_d), O.P(w_d), O.P(b_d), O.P(out))
+    out = O.gemm_geglu(a_d, w_d, b_d)
     pr = _q(A, dt) @ _q(Wt, dt).T + bias
     h, g = pr.chunk(2, dim=-1)
     assert O.rel_err(out, h * F.gelu(g)) < TOL[dt]
@@ -524,10 +523,7 @@ def test_gemm_pingpong_bit_exact(device, M, N, K, res, conv, dt):
                 A = _dev(_r(M, C, seed=300), dt, device)
                 W = _r(8 * C, C, seed=301, scale=1 / math.sqrt(C))[geglu64_order(8 * C)]
                 b = _r(8 * C, seed=302)
-                out = torch.empty(M, 4 * C, dtype=dt, device=device)
-                L.call("irx_op_gemm_geglu", O.S(), O.DT[dt], M, 8 * C, C, O.P(A), O.P(_dev(W, dt, device)),
-                       O.P(b.to(device).contiguous()), O.P(out))
-                outs.append(out)
+                outs.append(O.gemm_geglu(A, _dev(W, dt, device), b.to(device).contiguous()))
             elif conv is not None:
                 n, h, w, ci, co = conv
                 x = _dev(_r(n, h, w, ci, seed=303), dt, device)
@@ -593,9 +589,7 @@ def test_attention_v3_vs_v2_and_head_major(device, dt, B, Lq, Lk, C, heads):
     qd, kd, vd = _dev(q, dt, device), _dev(k, dt, device), _dev(v, dt, device)
     got = O.attention(qd, kd, vd, heads)
     hm = [x.view(B, x.shape[1], heads, d).transpose(1, 2).contiguous() for x in (qd, kd, vd)]
-    o = torch.empty(B, heads, Lq, d, dtype=dt, device=device)
-    L.call("irx_op_attention_hm", O.S(), O.DT[dt], B, heads, Lq, Lk, d, O.P(hm[0]), O.P(hm[1]), O.P(hm[2]),
-           O.P(o), 1.0 / math.sqrt(d))
+    o = O.attention_hm(hm[0], hm[1], hm[2])
     assert torch.equal(o.transpose(1, 2).reshape(B, Lq, C), got)
     ref = O.ref_attention(_q(q, dt), _q(k, dt), _q(v, dt), heads)
     assert O.rel_err(got, ref) < 2 * TOL[dt]
@@ -676,12 +670,8 @@ def test_gemm_sk_geglu(device, M, dt):
     perm = geglu64_order(8 * C)
     a_d, w_d, b_d = _dev(A, dt, device), _dev(Wt[perm], dt, device), bias[perm].to(device).contiguous()
 
-    def run():
-        buf = torch.full((M + 8, 4 * C), 1234.0, dtype=dt, device=device)   # 8 guard rows: no write past M
-        L.call("irx_op_gemm_geglu", O.S(), O.DT[dt], M, 8 * C, C, O.P(a_d), O.P(w_d), O.P(b_d), O.P(buf))
-        torch.cuda.synchronize()
-        assert bool((buf[M:] == 1234.0).all()), "GEGLU GEMM wrote past its last output row"
-        return buf[:M]
+    def run():   # (a guarded output: a full tile of sentinel rows behind row M, no write past it)
+        return O.gemm_geglu(a_d, w_d, b_d)
     sk = _with_sk(1, run)
     pr = _q(A, dt) @ _q(Wt, dt).T + bias
     h, g = pr.chunk(2, dim=-1)
@@ -966,3 +956,47 @@ def test_small_m_splitk(device, dt, M, N, K, act, res):
     assert O.rel_err(got, ref) < TOL[dt]
     assert O.rel_err(got, plain.float()) < (8e-3 if dt == torch.bfloat16 else 2e-3)
     assert torch.equal(got[:6], six)
+
+
+# ------------------------------------------------------------------ outputs of a wider row stride (ldc / ldo > columns)
+def _ld_gemm(M, N, K, res, opts):
+    def run(device, dt, ld_pad):
+        from image_restoration_and_enhancement_amd import _lib as L
+        A = _dev(_r(M, K, seed=400), dt, device)
+        Bw = _dev(_r(N, K, seed=401, scale=1 / math.sqrt(K)), dt, device)
+        R = _dev(_r(M, N, seed=402), dt, device) if res else None
+        with L.option(**opts):
+            return O.gemm(A, Bw, bias=_r(N, seed=403).to(device), residual=R, ld_pad=ld_pad)
+    return run
+
+
+def _ld_attn(B, Lq, Lk, C, heads):
+    def run(device, dt, ld_pad):
+        q, k, v = (_dev(_r(B, L_, C, seed=404 + i), dt, device) for i, L_ in enumerate((Lq, Lk, Lk)))
+        return O.attention(q, k, v, heads, ld_pad=ld_pad)
+    return run
+
+
+LD_PAD_CASES = {
+    "gemm_4wave": _ld_gemm(300, 2560, 320, False, dict(large_tiles=0)),
+    "gemm_large": _ld_gemm(5000, 640, 640, True, {}),
+    "gemm_splitk_reduce_kernel": _ld_gemm(1024, 1280, 2560, True, dict(splitk_inkernel=0)),
+    "gemm_splitk_inkernel": _ld_gemm(1024, 1280, 2560, True, dict(splitk_inkernel=1)),
+    "gemm_sk": _ld_gemm(777, 640, 320, True, dict(gemm_sk=3)),
+    "attention_d40": _ld_attn(1, 333, 190, 320, 8),
+    "attention_d80": _ld_attn(1, 100, 100, 640, 8),
+    "attention_d160": _ld_attn(1, 300, 300, 1280, 8),
+    "attention_d512": _ld_attn(1, 333, 333, 512, 1),
+}
+
+
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("case", list(LD_PAD_CASES))
+def test_output_row_stride_pad(device, case, dt):
+    """ldc = N + 8 / ldo = C + 8: columns past the logical width are another tensor's (the guarded buffer holds
+    sentinels there and checks them), and the result is bit for bit that of the dense output."""
+    from tests import guard as G
+    run = LD_PAD_CASES[case]
+    dense, padded = run(device, dt, 0), run(device, dt, 8)
+    assert padded.stride(-2) == dense.shape[-1] + 8 and dense.is_contiguous()
+    assert G.same(padded, dense)
