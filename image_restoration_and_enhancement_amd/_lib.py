@@ -181,6 +181,8 @@ _SIGS = {
     "irx_op_gemm_geglu": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "irx_op_gemm_ln_out": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, f32]),
     "irx_op_gemm_ln_fold": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "irx_op_gemm_ln_out_w": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, i32, i32, f32]),
+    "irx_op_gemm_ln_fold_w": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "irx_op_conv2d_gn_parts": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32,
                                      i32, i32, i32, i32, vp, i64, vp, vp, i32, i32, vp, vp, C.POINTER(i32),
                                      C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]),

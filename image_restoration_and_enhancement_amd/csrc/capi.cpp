@@ -1045,16 +1045,20 @@ int irx_op_attention_hm(void* s, int dtype, int B, int H, int lq, int lk, int d,
   IRX_API_END
 }
 
-int irx_op_gemm_ln_out(void* s, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,
-                       const void* residual, void* C, void* parts, int final_rs, float eps) {
+int irx_op_gemm_ln_out_w(void* s, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,
+                         const void* residual, long res_rows, void* C, void* parts, int width, int final_rs,
+                         float eps) {
   IRX_API_BEGIN
+  IRX_CHECK(width == kLnGroup || width == kLnGroupNarrow, "LayerNorm partials span 320 or 128 columns");
+  IRX_CHECK(!res_rows || (residual && res_rows > 0 && M <= 2 * res_rows), "res_rows: a residual, M <= 2 res_rows");
   GemmArgs a;
   a.dtype = dtype; a.M = M; a.N = N; a.K = K;
   a.A = A; a.lda = K; a.B = B; a.ldb = K;
   a.C = C; a.ldc = N; a.bias = bias;
-  a.residual = residual; a.ldr = N;
+  a.residual = residual; a.ldr = N; a.res_rows = res_rows;
   a.imgs = g_op_imgs;
   a.ln_out_rs = final_rs;
+  a.ln_W = width;
   a.ln_eps = eps;
   IRX_CHECK(parts && gemm_emits_ln_parts(a), "shape/dtype cannot emit LayerNorm partials");
   a.ln_out = (float2*)parts;
@@ -1062,10 +1066,21 @@ int irx_op_gemm_ln_out(void* s, int dtype, int M, int N, int K, const void* A, c
   IRX_API_END
 }
 
+int irx_op_gemm_ln_out(void* s, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,
+                       const void* residual, void* C, void* parts, int final_rs, float eps) {
+  return irx_op_gemm_ln_out_w(s, dtype, M, N, K, A, B, bias, residual, 0, C, parts, kLnGroup, final_rs, eps);
+}
+
 int irx_op_gemm_ln_fold(void* s, int dtype, int M, int N, int K, const void* A, const void* B, const float* u,
                         const float* v, const void* rs, const void* parts, int T, int geglu, void* C) {
+  return irx_op_gemm_ln_fold_w(s, dtype, M, N, K, A, B, u, v, rs, parts, T, kLnGroup, geglu, C);
+}
+
+int irx_op_gemm_ln_fold_w(void* s, int dtype, int M, int N, int K, const void* A, const void* B, const float* u,
+                          const float* v, const void* rs, const void* parts, int T, int width, int geglu, void* C) {
   IRX_API_BEGIN
   IRX_CHECK((rs != nullptr) != (parts != nullptr), "give the row statistics or the partials, not both");
+  IRX_CHECK(width == kLnGroup || width == kLnGroupNarrow, "LayerNorm partials span 320 or 128 columns");
   GemmArgs a;
   a.dtype = dtype; a.M = M; a.N = N; a.K = K;
   a.A = A; a.lda = K; a.B = B; a.ldb = K;
@@ -1074,6 +1089,7 @@ int irx_op_gemm_ln_fold(void* s, int dtype, int M, int N, int K, const void* A, 
   a.ln_rs = (const float2*)rs;
   a.ln_part = (const float2*)parts;
   a.ln_T = parts ? T : 0;
+  a.ln_W = width;
   a.imgs = g_op_imgs;
   IRX_CHECK(!geglu || gemm_geglu_fusable(a), "shape/dtype not eligible for the fused GEGLU epilogue");
   IRX_CHECK(gemm_ln_foldable(a), "shape/dtype not eligible for the folded LayerNorm epilogue");

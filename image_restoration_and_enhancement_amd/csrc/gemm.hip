@@ -291,7 +291,9 @@ void gemm(const GemmArgs& a, hipStream_t s) {
     IRX_CHECK(!a.A1 || (a.batch == 1 && a.kA1 > 0 && a.kA1 < a.K && a.lda1 % vec == 0 && ((uintptr_t)a.A1 % 16) == 0),
               "second A source: batch 1, 0 < kA1 < K, 16-byte rows");
   }
-  IRX_CHECK(!a.ln_part || (a.ln_T >= 1 && a.K == a.ln_T * kLnGroup), "LayerNorm partials must cover the K row");
+  IRX_CHECK(!(a.ln_part || a.ln_out) || a.ln_W == kLnGroup || a.ln_W == kLnGroupNarrow,
+            "LayerNorm partials span 320 or 128 columns");
+  IRX_CHECK(!a.ln_part || (a.ln_T >= 1 && a.K == a.ln_T * a.ln_W), "LayerNorm partials must cover the K row");
   // one plan per call (gemm_plan.cpp): the path, and whether it honours every feature the arguments request — the
   // answers the gemm_* queries gave the caller
   const GemmPlan p = gemm_plan(a);

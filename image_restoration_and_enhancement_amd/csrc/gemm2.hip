@@ -160,7 +160,15 @@ __global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 
   constexpr int RINGX = RING + (!HALO && NINST % NW ? 64 : 0);
   constexpr int SMEM = RINGX > BM * BN / 8 ? RINGX : BM * BN / 8;
   static_assert(SMEM * 16 <= 160 * 1024, "LDS budget");
-  __shared__ __attribute__((aligned(16))) uint4 smem[SMEM];
+  // folded LayerNorm (GemmArgs::ln_rs / ln_part): the (rstd, rstd * mean) pairs of the block's BM rows, merged from
+  // the producer's partials once per block before the main loop (ln_table below) and read by the epilogue.  BM x 8
+  // bytes behind the ring and the epilogue's staging tile, which overwrite neither.  Dense 16-bit tiles wherever it
+  // fits (not the 256x320 tile, whose staging tile is all 160 KiB: its epilogue merges per row, ln_rs_at)
+  constexpr bool LNTAB = !CONV && !OUTF32 && HALO == 0 && SMEM * 16 + BM * 8 <= 160 * 1024;
+  constexpr int LNT_U4 = LNTAB ? BM / 2 : 0;
+  static_assert(!LNTAB || NT >= BM, "one thread per table row");
+  __shared__ __attribute__((aligned(16))) uint4 smem[SMEM + LNT_U4];
+  float2* const lnT = (float2*)(smem + SMEM);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -326,6 +334,18 @@ __global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 
         for (int j = 0; j < TN; ++j)
           acc[i][j] = Mfma<T>::m16x16x32(af[i], bfr[j], acc[i][j]);
       if constexpr (S > 2) __builtin_amdgcn_s_setprio(0);
+    }
+  };
+
+  // The block's LayerNorm table (LNTAB): thread r < BM merges row m0 + r's partials in ascending order (ln_rs_at's
+  // arithmetic: the bits the per-row form gives) or copies its ln_rs pair; rows past M get (0, 0).  Called once the
+  // first ring stages are in flight; the barrier that ends the main loop orders it before the epilogue's reads.
+  auto ln_table = [&]() {
+    if constexpr (LNTAB) {
+      if ((a.ln_rs || a.ln_part) && tid < BM) {
+        const long m = m0 + tid;
+        lnT[tid] = m < a.M ? ln_rs_at(a.ln_rs, a.ln_part, a.ln_T, a.ln_eps, m, a.ln_W) : make_float2(0.f, 0.f);
+      }
     }
   };
 
@@ -896,6 +916,7 @@ __global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 
     };
     issueP(kt0, 0);
     issueP(min(kt0 + 1, kt1 - 1), 1);
+    ln_table();                                          // (its loads are younger than the DMA: the wait below holds)
     wait_vm(IPW);                                        // step kt0 landed
     barrier(true);
     if (g1) barrier(true);
@@ -919,6 +940,7 @@ __global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 
     __syncthreads();
   } else if constexpr (S == 2) {
     if (kt0 < kt1) issue(kt0, 0);
+    ln_table();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int kt = kt0; kt < kt1; ++kt) {
@@ -933,6 +955,7 @@ __global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 
 #pragma unroll
     for (int p = 0; p < S - 1; ++p)
       if (kt0 + p < kt1) issue(kt0 + p, p);
+    ln_table();   // (younger than the DMA pieces: the counted waits below only get stricter)
     int st = 0;
     for (int kt = kt0; kt < kt1; ++kt) {
       // this wave's pieces of step kt have landed once at most min(S-2, kt1-1-kt) younger stages remain
@@ -1067,8 +1090,10 @@ __global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int row = wm * TM * 16 + i * 16 + fgrp * 4 + r;
-            const float2 rs = m0 + row < a.M ? ln_rs_at(a.ln_rs, a.ln_part, a.ln_T, a.ln_eps, m0 + row)
-                                             : make_float2(0.f, 0.f);
+            float2 rs;   // (the block's table where the tile has one: merged once per block, not per N tile and row)
+            if constexpr (LNTAB) rs = lnT[row];
+            else rs = m0 + row < a.M ? ln_rs_at(a.ln_rs, a.ln_part, a.ln_T, a.ln_eps, m0 + row, a.ln_W)
+                                     : make_float2(0.f, 0.f);
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
               const int col = wn * TN * 16 + j * 16 + frow;
@@ -1271,9 +1296,12 @@ __global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 
         }
         return;
       }
-      // LayerNorm partials of the output (GemmArgs::ln_out; host: gemm_emits_ln_parts, BN == kLnGroup): the final
-      // values are written back over the staged tile, then G threads per row reduce it in two passes
-      float2* const lno = BN == kLnGroup ? a.ln_out : nullptr;
+      // LayerNorm partials of the output (GemmArgs::ln_out; host: gemm_emits_ln_parts, BN == ln_W): the final
+      // values are written back over the staged tile, then G threads per row reduce it in one shifted pass.  One
+      // partial per tile and row: the 320-column tiles, and the 8-wave 128x128 two-stage tile (C = 1280 projections)
+      constexpr bool LNOUT = (BN == kLnGroup && NT % BM == 0) ||
+                             (BN == kLnGroupNarrow && BM == 128 && NW == 8 && !CONV && !PP && HALO == 0);
+      float2* const lno = LNOUT ? a.ln_out : nullptr;
       // head-split output (attention operands, GemmArgs::hs_L) with nothing to add: the tile's columns are whole
       // heads of one q / k / v part and its rows one image's tokens, so each head segment of the tile is one
       // contiguous [BM][hs_d] block of C.  Chunks are walked segment-major (consecutive lanes write consecutive
@@ -1338,7 +1366,7 @@ __global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 
         if (m0 + row >= a.M || n0 + c * 8 >= a.N) continue;
         store_chunk(row, c);
       }
-      if constexpr (BN == kLnGroup && NT % BM == 0) {
+      if constexpr (LNOUT) {
         if (lno) {
           // G adjacent lanes per row, each over CPR / G chunks: mean, then the sum of squared deviations from it
           constexpr int G = NT / BM, CPG = CPR / G;
@@ -1371,11 +1399,11 @@ __global__ __launch_bounds__(WM * WN * 64, pp_pair(PP, BM, BN) ? 4 : WM * WN == 
             s1 += __shfl_xor(s1, o);
             s2 += __shfl_xor(s2, o);
           }
-          const float ds = s1 * (1.f / (float)kLnGroup);
+          const float ds = s1 * (1.f / (float)BN);
           if (g == 0 && m0 + row < a.M) {
             const float mean = x0 + ds, m2 = fmaxf(fmaf(-s1, ds, s2), 0.f);
-            lno[(long)(m0 + row) * (a.N / kLnGroup) + n0 / kLnGroup] =
-                a.ln_out_rs ? ln_fin(mean, m2, 1, a.ln_eps) : make_float2(mean, m2);
+            lno[(long)(m0 + row) * (a.N / BN) + n0 / BN] =
+                a.ln_out_rs ? ln_fin(mean, m2, 1, a.ln_eps, BN) : make_float2(mean, m2);
           }
         }
       }

@@ -55,7 +55,10 @@ int g_gn_parts = 1;      // 1: producers emit GroupNorm partial sums, the stats 
 int g_gn_red_parts = 1;  // irx_set_option("gn_red_parts", 0): split-K reduce kernels do not emit GroupNorm partials (A/B)
 int g_gn_fold = 1;       // 1: the transformer GroupNorm folded into per-image proj_in weights (0: gn_apply, A/B)
 int g_ln_fold = 1;       // 1: 16-bit UNets fold LayerNorm into the following projections (read at model creation)
-int g_ln_parts = 1;      // 1: transformer producers emit LayerNorm partials, the statistics pass is skipped (0: A/B)
+// transformer producers emit LayerNorm partials, the statistics pass is skipped: 0 off (A/B), 1 at C == 320 only (final
+// pairs; the default), 2 at every width (C = 640 / 1280: per-tile partials merged by the consumer blocks — 2.2 ms/step
+// faster in the same-box A/B, short of the 3 x spread the default asks for: DESIGN.md §22)
+int g_ln_parts = 1;
 
 namespace {
 
@@ -501,12 +504,17 @@ GemmPlan gemm_plan(const GemmArgs& a) {
     p.ln_fold = !a.conv && a.alpha == 1.f && one16 && vec_ok(a) && (p.path == GEMM_SK || (p.path == GEMM_LARGE && full_epi));
   // LayerNorm partials out and per-image B / bias: the staged epilogue of the two-stage / lean ping-pong loops
   const bool staged = p.path == GEMM_LARGE && full_epi && !a.conv && one16 && !a.geglu && g_gemm_deep == 0;
-  if (a.ln_out && g_ln_parts && staged && !a.hs_L && !a.gn_part && a.N % kLnGroup == 0 && !(a.ln_out_rs && a.N != kLnGroup)) {
-    // 320-column tiles (the 64x64 / 32x32-level transformer projections).  A call that gemm_sk takes without the
-    // partials (option gemm_sk 3) stays there: its consumer runs the statistics pass
+  const bool ln_w_ok = a.ln_W == kLnGroup || a.ln_W == kLnGroupNarrow;
+  if (a.ln_out && g_ln_parts && staged && !a.hs_L && !a.gn_part && ln_w_ok && a.N % a.ln_W == 0 &&
+      !(a.ln_out_rs && a.N != a.ln_W)) {
+    // one partial per tile and row: the tile as wide as the requested group — 320-column tiles (the 64x64 / 32x32-level
+    // transformer projections) or the 8-wave 128x128 two-stage tile (C = 1280).  A call that gemm_sk takes without
+    // the partials (option gemm_sk 3) stays there: its consumer runs the statistics pass
     GemmArgs bare = a;
     bare.ln_out = nullptr;
-    p.ln_out = p.BN == kLnGroup && (p.BM == 256 || p.BM == 128) && !gemm_sk_eligible(bare);
+    const bool tile = a.ln_W == kLnGroup ? (p.BM == 256 || p.BM == 128)
+                                         : (p.BM == 128 && p.WM * p.WN == 8 && !p.PP);
+    p.ln_out = p.BN == a.ln_W && tile && !gemm_sk_eligible(bare);
   }
   // ... row tiles that never straddle two images
   if (a.b_rows > 0)   // (not the 4-wave 128-row tiles of option gemm_small)

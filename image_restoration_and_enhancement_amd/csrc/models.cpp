@@ -472,7 +472,7 @@ Act Unet::resnet(Ctx& c, const ResW& r, Act& x0, Act* x1, const float* tproj, lo
 }
 
 void Unet::ln_gemm(Ctx& c, GemmArgs& g, const void* x, int rows, int C, P lnw, P lnb, P u, P v, const float* bias,
-                   void* nbuf, float2* st, const float2* parts) {
+                   void* nbuf, float2* st, LnStats parts) {
   g.lda = C;
   if (!ln_fold_) {
     lnorm(c, x, rows, C, lnw, lnb, 1e-5f, nbuf);
@@ -482,9 +482,11 @@ void Unet::ln_gemm(Ctx& c, GemmArgs& g, const void* x, int rows, int C, P lnw, P
     g.bias = fptr(v);                 // bias + W beta
     g.A = x;
     g.ln_u = fptr(u);
-    g.ln_rs = parts ? parts : st;     // (the producer of x wrote its rows' statistics: no pass over x)
+    // (the producer of x wrote its rows' statistics: no pass over x)
+    if (parts.p && parts.T > 0) { g.ln_part = parts.p; g.ln_T = parts.T; g.ln_W = parts.W; }
+    else g.ln_rs = parts.p ? parts.p : st;
     if (gemm_ln_foldable(g)) {
-      if (!parts && !c.ws->dry()) layer_norm_stats(dt_, x, C, rows, C, 1e-5f, st, c.s);
+      if (!parts.p && !c.ws->dry()) layer_norm_stats(dt_, x, C, rows, C, 1e-5f, st, c.s);
     } else {                          // (W * gamma, bias + W beta) after an affine-free LayerNorm
       g.ln_rs = nullptr;
       g.ln_part = nullptr;
@@ -496,7 +498,7 @@ void Unet::ln_gemm(Ctx& c, GemmArgs& g, const void* x, int rows, int C, P lnw, P
   run_gemm(c, g);
 }
 
-const float2* Unet::xf_proj(Ctx& c, const void* A, int M, int C, P w, const float* bias, void* out,
+LnStats Unet::xf_proj(Ctx& c, const void* A, int M, int C, P w, const float* bias, void* out,
                             const void* residual, int imgs, float2* lnp, long res_rows) {
   GemmArgs a;
   a.dtype = dt_;
@@ -507,12 +509,26 @@ const float2* Unet::xf_proj(Ctx& c, const void* A, int M, int C, P w, const floa
   a.bias = bias;
   a.residual = residual; a.ldr = C; a.res_rows = res_rows;
   a.imgs = imgs;
-  a.ln_out_rs = 1;
   a.ln_eps = 1e-5f;
-  const bool emit = lnp && gemm_emits_ln_parts(a);   // (shape-only decision: the dry run decides the same)
-  if (emit) a.ln_out = lnp;
+  // (shape-only decisions: the dry run decides the same)
+  LnStats st;
+  if (lnp && C == kLnGroup) {   // the whole row in one tile: final pairs
+    a.ln_out_rs = 1;
+    if (gemm_emits_ln_parts(a)) st.p = lnp;
+  } else if (lnp) {             // partials of the planned tile's width
+    for (int W : {kLnGroup, kLnGroupNarrow}) {
+      if (C % W) continue;
+      a.ln_W = W;
+      if (gemm_emits_ln_parts(a)) {
+        st.p = lnp; st.T = C / W; st.W = W;
+        break;
+      }
+    }
+  }
+  if (st.p) a.ln_out = lnp;
+  else { a.ln_out_rs = 0; a.ln_W = kLnGroup; }
   run_gemm(c, a);
-  return emit ? lnp : nullptr;
+  return st;
 }
 
 Act Unet::transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L, bool dup) {
@@ -525,11 +541,15 @@ Act Unet::transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L, bool 
   const int heads = cfg_.heads, d = C / heads;
   const float scale = 1.0f / std::sqrt((float)d);
   Act h = new_act(c, B, x.h, x.w, C);
-  // LayerNorm row statistics of the residual stream h, written by the projections that write it (GemmArgs::ln_out,
-  // final (rstd, rstd * mean) rows: C == 320, the 64x64 level, where a 320-column tile holds the whole row; the
-  // wider levels keep the statistics pass — their two-partial merge in the consumers' epilogues measured slower)
-  float2* lnp = (ln_fold_ && C == kLnGroup) ? (float2*)c.ws->alloc(Mo * sizeof(float2)) : nullptr;
-  const float2* parts = nullptr;
+  // LayerNorm row statistics of the residual stream h, written by the projections that write it (GemmArgs::ln_out):
+  // final (rstd, rstd * mean) rows at C == 320, the 64x64 level, where a 320-column tile holds the whole row; at the
+  // wider levels (option ln_parts 2) one partial per producer tile and row — C / 128 per row at most — which each
+  // consumer block merges once for its rows (gemm2.hip, LNTAB)
+  const bool ln_wide = ln_fold_ && g_ln_parts >= 2 && C != kLnGroup && C % kLnGroupNarrow == 0;
+  float2* lnp = (ln_fold_ && C == kLnGroup) ? (float2*)c.ws->alloc(Mo * sizeof(float2))
+                : ln_wide                   ? (float2*)c.ws->alloc(Mo * (C / kLnGroupNarrow) * sizeof(float2))
+                                            : nullptr;
+  LnStats parts;
   // GroupNorm (no SiLU) -> proj_in: folded into per-image weights where they stay small next to the activation
   // (C == 320, the 64x64 level: 16 x 200 KB against 2 x 42 MB of gn_apply traffic; at 32x32 the 13 MB of per-image
   // weights cost what they save): proj_in(GN(x)) = x (W diag(a_i))^T + (bias + W b_i) for image i with
@@ -556,7 +576,7 @@ Act Unet::transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L, bool 
     pg.ln_eps = 1e-5f;
     if (lnp && gemm_emits_ln_parts(pg)) {
       pg.ln_out = lnp;
-      parts = lnp;
+      parts.p = lnp;   // (final pairs: C <= 320 here)
     }
     run_gemm(c, pg);
     c.ws->free(mr);

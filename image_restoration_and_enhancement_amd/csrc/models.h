@@ -131,6 +131,10 @@ struct ResW {
   long temb_off = -1;     // column offset into the fused time_emb_proj output (UNet only)
 };
 
+// LayerNorm row statistics a producer's epilogue wrote (GemmArgs::ln_out): the final (rstd, rstd * mean) pairs
+// (T == 0) or T partials of W columns per row; p == nullptr: none, the consumer runs the statistics pass
+struct LnStats { const float2* p = nullptr; int T = 0; int W = 0; };
+
 class Unet : public Model {
  public:
   Unet(const irx_model_config& cfg, int dtype);
@@ -182,15 +186,16 @@ class Unet : public Model {
   // x.n images, cross-attention reads that Q against the K|V of 2 x.n images, and the result has 2 x.n images
   Act transformer(Ctx& c, const XfW& a, Act& x, const void* kv, int L, bool dup = false);
   // LayerNorm(x) -> projection g (g.A / lda / bias set here): folded into g's epilogue when ln_fold_ and the shape
-  // takes it — with the statistics from `parts` (the producer of x emitted them, GemmArgs::ln_out) or from a
-  // statistics pass written to `st` — else through the normalised copy `nbuf`
+  // takes it — with the statistics from `parts` (the producer of x emitted them) or from a statistics pass written
+  // to `st` — else through the normalised copy `nbuf`
   void ln_gemm(Ctx& c, GemmArgs& g, const void* x, int rows, int C, P lnw, P lnb, P u, P v, const float* bias,
-               void* nbuf, float2* st, const float2* parts = nullptr);
+               void* nbuf, float2* st, LnStats parts = LnStats());
   // a transformer projection that writes the residual stream (proj_in, to_out, to_out2): out = A W^T + bias
-  // (+ residual), emitting the output's LayerNorm partials into `lnp` where the epilogue can; returns lnp or null
+  // (+ residual), emitting the output's LayerNorm statistics into `lnp` where the epilogue can: final pairs at
+  // C == 320, else partials per 320- or 128-column tile, whichever the planned tile gives (option ln_parts 2)
   // (res_rows: the residual repeats every res_rows rows, GemmArgs::res_rows)
-  const float2* xf_proj(Ctx& c, const void* A, int M, int C, P w, const float* bias, void* out, const void* residual,
-                        int imgs, float2* lnp, long res_rows = 0);
+  LnStats xf_proj(Ctx& c, const void* A, int M, int C, P w, const float* bias, void* out, const void* residual,
+                  int imgs, float2* lnp, long res_rows = 0);
 
   int cin_pad_ = 8;
   bool ln_fold_ = false;   // LayerNorm folded into the transformer projections (fixed at creation: the blob layout)

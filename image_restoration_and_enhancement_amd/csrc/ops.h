@@ -68,14 +68,19 @@ struct GemmArgs {
   // exactly LN(x) W^T + bias, with no normalised copy of A written or read.
   const float2* ln_rs = nullptr; const float* ln_u = nullptr;
   // ... or the row statistics as producer partials (ln_out of the GEMM that wrote A): ln_part[m * ln_T + t] = (mean,
-  // M2) of row m over 320-column group t of a ln_T * 320-wide row, merged in the epilogue into
-  // (rstd, rstd * mean) with rstd = rsqrt(M2 / (ln_T * 320) + ln_eps) (ln_rs_at) — no statistics pass over A
+  // M2) of row m over ln_W-column group t of a ln_T * ln_W-wide row, merged into (rstd, rstd * mean) with
+  // rstd = rsqrt(M2 / (ln_T * ln_W) + ln_eps) (ln_rs_at) — no statistics pass over A.  The large tiles merge a
+  // block's BM rows once, before the main loop, into an LDS table the epilogue reads (gemm2.hip, LNTAB)
   const float2* ln_part = nullptr; int ln_T = 0; float ln_eps = 1e-5f;
+  // columns per LayerNorm partial, of ln_part and of ln_out alike: kLnGroup (320) or kLnGroupNarrow (128) — the
+  // producer's tile width, one partial per tile and row
+  int ln_W = 320;
   // LayerNorm partials of the OUTPUT emitted by the epilogue (gemm_emits_ln_parts: the transformer's residual stream,
-  // whose next consumer folds its LayerNorm): per output row m and 320-column group t, (mean, M2 = sum of squared
-  // deviations from that mean) of the stored values, two-pass over the staged tile, at ln_out[m * (N / 320) + t]
+  // whose next consumer folds its LayerNorm): per output row m and ln_W-column group t, (mean, M2 = sum of squared
+  // deviations from that mean) of the stored values, one shifted pass over the staged tile, at
+  // ln_out[m * (N / ln_W) + t]
   float2* ln_out = nullptr;
-  // ... and with ln_out_rs (N == 320: the whole row in one group) the final (rstd, rstd * mean) of each row with
+  // ... and with ln_out_rs (N == ln_W: the whole row in one group) the final (rstd, rstd * mean) of each row with
   // ln_eps instead — what a folded consumer takes as ln_rs, no merge left
   int ln_out_rs = 0;
   // per-image operands (GroupNorm folded into the weights, gn_fold_weights): rows [i * b_rows, (i + 1) * b_rows) are
@@ -98,22 +103,24 @@ struct GemmArgs {
   int dbg = 0;            // large-tile diagnostics (irx_set_option("gemm_dbg")): 1 skip epilogue, 2 skip MFMAs
 };
 constexpr int kCanonImages = 16;
-constexpr int kLnGroup = 320;   // columns per LayerNorm partial (GemmArgs::ln_out / ln_part)
-// LayerNorm row statistics from producer partials (mean_t, M2_t) over T equal 320-column groups: the merged (mean, M2)
-// (two groups: M2 = M2_a + M2_b + 160 (mean_a - mean_b)^2; mean = (mean_a + mean_b) / 2, both exact reassociations of
-// the pooled sums) and the (rstd, rstd * mean) the folded epilogue applies.  Multiplies by exact reciprocals only
-// (no division): the same arithmetic wherever it runs (gemm2 / gemm_sk epilogues).
-__device__ __forceinline__ float2 ln_fin(float mean, float m2, int T, float eps) {
-  const float inv_n = T == 1 ? 1.f / 320.f : T == 2 ? 1.f / 640.f : 1.f / (float)(T * kLnGroup);
+constexpr int kLnGroup = 320;   // columns per LayerNorm partial (GemmArgs::ln_out / ln_part) ...
+constexpr int kLnGroupNarrow = 128;   // ... or, from producers on 128-column tiles (GemmArgs::ln_W)
+// LayerNorm row statistics from producer partials (mean_t, M2_t) over T equal W-column groups: the merged (mean, M2)
+// (two groups: M2 = M2_a + M2_b + W / 2 (mean_a - mean_b)^2; mean = (mean_a + mean_b) / 2, both exact reassociations
+// of the pooled sums; more: the mean of the means, then M2 = sum_t M2_t + W (mean_t - mean)^2 in ascending t) and the
+// (rstd, rstd * mean) the folded epilogue applies.  The same arithmetic wherever it runs (gemm2 / gemm_sk); at
+// W == 320 the T == 1 and T == 2 forms multiply by constant reciprocals, as they always did.
+__device__ __forceinline__ float2 ln_fin(float mean, float m2, int T, float eps, int W = kLnGroup) {
+  const float inv_n = W == kLnGroup && T == 1 ? 1.f / 320.f : W == kLnGroup && T == 2 ? 1.f / 640.f : 1.f / (float)(T * W);
   const float rstd = rsqrtf(fmaf(m2, inv_n, eps));
   return make_float2(rstd, rstd * mean);
 }
-__device__ __forceinline__ float2 ln_merge(const float2* __restrict__ p, int T) {   // -> (mean, M2)
+__device__ __forceinline__ float2 ln_merge(const float2* __restrict__ p, int T, int W = kLnGroup) {   // -> (mean, M2)
   if (T == 1) return p[0];
   if (T == 2) {
     const float2 x = p[0], y = p[1];
     const float d = x.x - y.x;
-    return make_float2((x.x + y.x) * 0.5f, fmaf(0.5f * (float)kLnGroup * d, d, x.y + y.y));
+    return make_float2((x.x + y.x) * 0.5f, fmaf(0.5f * (float)W * d, d, x.y + y.y));
   }
   float sm = 0.f;
   for (int t = 0; t < T; ++t) sm += p[t].x;
@@ -122,16 +129,16 @@ __device__ __forceinline__ float2 ln_merge(const float2* __restrict__ p, int T) 
   for (int t = 0; t < T; ++t) {
     const float2 v = p[t];
     const float d = v.x - mean;
-    m2 += fmaf((float)kLnGroup * d, d, v.y);
+    m2 += fmaf((float)W * d, d, v.y);
   }
   return make_float2(mean, m2);
 }
-// (rstd, rstd * mean) of row m: ln_rs[m], or merged from the row's ln_T producer partials
+// (rstd, rstd * mean) of row m: ln_rs[m], or merged from the row's ln_T producer partials over W columns each
 __device__ __forceinline__ float2 ln_rs_at(const float2* __restrict__ rs, const float2* __restrict__ part, int T,
-                                           float eps, long m) {
+                                           float eps, long m, int W = kLnGroup) {
   if (!part) return rs[m];
-  const float2 v = ln_merge(part + m * T, T);
-  return ln_fin(v.x, v.y, T, eps);
+  const float2 v = ln_merge(part + m * T, T, W);
+  return ln_fin(v.x, v.y, T, eps, W);
 }
 // element offset of output (m, n) in C (see GemmArgs::hs_L).  Fields passed by value: a reference to the
 // kernel-argument struct would make the compiler copy all of it to scratch.
@@ -198,7 +205,9 @@ extern int g_gn_parts;     // 1: producers emit GroupNorm partial sums, the stat
 extern int g_gn_red_parts;   // 1: split-K reduce kernels emit GroupNorm partials (per 64-row block)
 extern int g_gn_fold;      // 1: the transformer GroupNorm folded into per-image proj_in weights (0: gn_apply, A/B)
 extern int g_ln_fold;      // 1: 16-bit UNets fold LayerNorm into the following projections (read at model creation)
-extern int g_ln_parts;     // 1: transformer producers emit LayerNorm partials, the statistics pass is skipped (0: A/B)
+// transformer producers emit LayerNorm partials, the statistics pass is skipped: 0 off (A/B), 1 at C == 320 only, 2 at
+// every width (C = 640 / 1280: partials per 320- or 128-column producer tile, merged by the consumer blocks)
+extern int g_ln_parts;
 // launch-side options (gemm_sk.hip, gemm2.hip) and the models' GEMM-shaped choices (models.cpp)
 extern int g_gemm_sk_blocks;
 extern int g_gemm_dbg;     // timing diagnostics only: results are wrong when set

@@ -502,6 +502,14 @@ int irx_op_gemm_ln_out(void* stream, int dtype, int M, int N, int K, const void*
    (parts, irx_op_gemm_ln_out; K = 320 T).  geglu != 0: B / u / v in the GEGLU64 row order, C gets N / 2 columns. */
 int irx_op_gemm_ln_fold(void* stream, int dtype, int M, int N, int K, const void* A, const void* B, const float* u,
                         const float* v, const void* rs, const void* parts, int T, int geglu, void* C);
+/* The same pair with the partial group width given: `width` = 320 or 128 columns per partial (the producer's tile
+   width: parts[m][N / width], K = width T), and for the producer a residual that repeats every res_rows rows
+   (0: one residual row per output row; M <= 2 res_rows). */
+int irx_op_gemm_ln_out_w(void* stream, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,
+                         const void* residual, long res_rows, void* C, void* parts, int width, int final_rs,
+                         float eps);
+int irx_op_gemm_ln_fold_w(void* stream, int dtype, int M, int N, int K, const void* A, const void* B, const float* u,
+                          const float* v, const void* rs, const void* parts, int T, int width, int geglu, void* C);
 /* GroupNorm statistics from producer partials: the 16-bit UNet / VAE GroupNorms read (sum, sum of squares) blocks
    written by the kernel that stored the tensor instead of making a statistics pass.  The three producers below run
    the GEMM exactly as the models do (same arguments, same plan, split-K partials from `ws`) and write, next to the

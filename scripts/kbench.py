@@ -86,6 +86,59 @@ def timeit(fn, iters):
     return a.elapsed_time(b) / iters
 
 
+def lnwide(args, dev, dt, g):
+    """The C = 640 / 1280 residual-stream producers (+ residual, in place) and their folded consumers at the bench's M
+    (16 images): `new` = this library emitting / merging partials, `rs` = this library fed statistics rows (what
+    option ln_parts 1 runs), `base` = the --base library's kernel for the same call (rows; producers: no partials)."""
+    import ctypes as C
+    libs = [("new", L.load())]
+    if args.base:
+        b = C.CDLL(args.base)
+        for n in ("irx_op_gemm_ln_fold", "irx_op_gemm", "irx_set_option"):
+            getattr(b, n).restype, getattr(b, n).argtypes = L._SIGS[n]
+        libs.append(("base", b))
+    for _, lib in libs:
+        lib.irx_set_option(b"op_imgs", 16)
+    d, S, P = O.DT[dt], O.S, O.P
+
+    def line(lab, runs, flops):
+        res = {n: [] for n, _ in runs}
+        for _ in range(3):
+            for n, fn in runs:
+                res[n].append(timeit(fn, args.iters) * 1e3)
+        print(f"{lab:34s} " + " | ".join(f"{n} {min(v):6.1f} - {max(v):6.1f} us" for n, v in res.items()), flush=True)
+
+    for M, Cn, W in ((16384, 640, 320), (4096, 1280, 128), (1024, 1280, 128)):
+        A = torch.randn(M, Cn, device=dev, generator=g).to(dt)
+        Bw = (torch.randn(Cn, Cn, device=dev, generator=g) / math.sqrt(Cn)).to(dt)
+        bias = torch.zeros(Cn, device=dev)
+        Cb = torch.randn(M, Cn, device=dev, generator=g).to(dt)
+        parts = torch.empty(M, Cn // W, 2, device=dev)
+        runs = [("new+lnout", lambda: L.call("irx_op_gemm_ln_out_w", S(), d, M, Cn, Cn, P(A), P(Bw), P(bias), P(Cb), 0,
+                                             P(Cb), P(parts), W, 0, 1e-5))]
+        for n, lib in libs:
+            runs.append((n, lambda lib=lib: lib.irx_op_gemm(S(), d, M, Cn, Cn, P(A), Cn, P(Bw), Cn, P(Cb), Cn, P(bias), 1.0, 0,
+                                                           P(Cb), Cn, 0, 1, 0, 0, 0, 0)))
+        line(f"producer M{M} N{Cn} K{Cn}", runs, 2.0 * M * Cn * Cn)
+        Af = A.float()
+        mean = Af.mean(-1)
+        rs = torch.stack([torch.rsqrt(Af.var(-1, unbiased=False) + 1e-5)] * 2, -1)
+        rs[:, 1] *= mean
+        rs = rs.contiguous()
+        L.call("irx_op_gemm_ln_out_w", S(), d, M, Cn, Cn, P(A), P(Bw), P(bias), None, 0, P(Cb), P(parts), W, 0, 1e-5)
+        for lab, N, geglu in (("lin", Cn, 0), ("qkv", 3 * Cn, 0), ("geglu", 8 * Cn, 1)):
+            Wc = (torch.randn(N, Cn, device=dev, generator=g) / math.sqrt(Cn)).to(dt)
+            u = Wc.float().sum(1).contiguous()
+            v = torch.zeros(N, device=dev)
+            out = torch.empty(M, N // 2 if geglu else N, dtype=dt, device=dev)
+            runs = [("new parts", lambda: L.call("irx_op_gemm_ln_fold_w", S(), d, M, N, Cn, P(Cb), P(Wc), P(u), P(v), None,
+                                                 P(parts), Cn // W, W, geglu, P(out)))]
+            for n, lib in libs:
+                runs.append((n + " rs", lambda lib=lib: lib.irx_op_gemm_ln_fold(S(), d, M, N, Cn, P(Cb), P(Wc), P(u), P(v),
+                                                                                P(rs), None, 0, geglu, P(out))))
+            line(f"consumer {lab} M{M} N{N} K{Cn}", runs, 2.0 * M * N * Cn)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -98,6 +151,10 @@ def main():
     ap.add_argument("--pair", action="store_true", help="the GEGLU / q|k|v projections with the LayerNorm fold: the default "
                     "kernel vs the two-per-CU ping-pong tiles (option gemm_pp2), alternated, two repeats")
     ap.add_argument("--lnout", action="store_true", help="residual-stream producers with / without LayerNorm partials")
+    ap.add_argument("--lnwide", action="store_true", help="C = 640 / 1280 residual-stream producers with / without "
+                    "LayerNorm partials and their folded consumers fed partials / statistics rows, this library and "
+                    "--base alternated, three repeats")
+    ap.add_argument("--base", default="", help="--lnwide: a second libirx.so (the parent commit's) timed in the same process")
     args = ap.parse_args()
     dev = torch.device("cuda")
     L.load()
@@ -121,6 +178,9 @@ def main():
     def setv(opts):
         for k, v in {**base, **opts}.items():
             L.call("irx_set_option", k.encode(), v)
+    if args.lnwide:
+        lnwide(args, dev, dt, g)
+        return
     if args.pair:   # the folded-LayerNorm projections of the bench step (M at 16 images), per shape: repeats x variants
         import ctypes as C
         setv({})
