@@ -177,6 +177,8 @@ _SIGS = {
     "irx_op_attention": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i64, i64, vp, i64, i64, vp, i64, i64, vp,
                                i64, i64, f32, i32]),
     "irx_op_attention_hm": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, f32]),
+    "irx_op_attention_ex": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64,
+                                  i64, vp, i64, i64, i64, f32, i32, i32]),
     "irx_op_geglu": (i32, [vp, i32, vp, i32, i32, vp]),
     "irx_op_gemm_geglu": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "irx_op_gemm_ln_out": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, f32]),

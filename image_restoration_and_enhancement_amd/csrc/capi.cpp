@@ -1045,6 +1045,22 @@ int irx_op_attention_hm(void* s, int dtype, int B, int H, int lq, int lk, int d,
   IRX_API_END
 }
 
+int irx_op_attention_ex(void* s, int dtype, int B, int H, int lq, int lk, int d, const void* q, long ldq, long sq,
+                        long hsq, const void* k, long ldk, long sk, long hsk, const void* v, long ldv, long sv,
+                        long hsv, void* o, long ldo, long so, long hso, float scale, int causal, int q_scaled) {
+  IRX_API_BEGIN
+  IRX_CHECK(q && k && v && o, "null buffer");
+  AttnArgs a;
+  a.dtype = dtype; a.B = B; a.H = H; a.Lq = lq; a.Lk = lk; a.d = d;
+  a.q = q; a.ldq = ldq; a.sq = sq; a.hsq = hsq;
+  a.k = k; a.ldk = ldk; a.sk = sk; a.hsk = hsk;
+  a.v = v; a.ldv = ldv; a.sv = sv; a.hsv = hsv;
+  a.o = o; a.ldo = ldo; a.so = so; a.hso = hso;
+  a.scale = scale; a.causal = causal; a.q_scaled = q_scaled ? 1 : 0;
+  attention(a, S(s));
+  IRX_API_END
+}
+
 int irx_op_gemm_ln_out_w(void* s, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,
                          const void* residual, long res_rows, void* C, void* parts, int width, int final_rs,
                          float eps) {

@@ -485,6 +485,13 @@ int irx_op_attention(void* stream, int dtype, int batch, int heads, int lq, int 
 /* heads laid out [batch][heads][len][d] (q, k, v and o), contiguous */
 int irx_op_attention_hm(void* stream, int dtype, int batch, int heads, int lq, int lk, int d, const void* q,
                         const void* k, const void* v, void* o, float scale);
+/* The launch as the models make it: every operand with its own row stride (ld*), batch stride (s*) and head stride
+   (hs*; 0 = heads interleaved in a row, stride d), all in elements, so head-major and row-major operands mix and K / V
+   may be column slices of a wider buffer.  q_scaled != 0: q already carries scale * log2(e) (folded into the to_q
+   weights), the kernel applies no scale of its own. */
+int irx_op_attention_ex(void* stream, int dtype, int batch, int heads, int lq, int lk, int d, const void* q, long ldq,
+                        long sq, long hsq, const void* k, long ldk, long sk, long hsk, const void* v, long ldv, long sv,
+                        long hsv, void* o, long ldo, long so, long hso, float scale, int causal, int q_scaled);
 int irx_op_geglu(void* stream, int dtype, const void* proj, int M, int F, void* out);
 /* C[M][N/2] = GEGLU(A B^T + bias) with B/bias in the GEGLU64 row order (fused epilogue, bf16 large tiles) */
 int irx_op_gemm_geglu(void* stream, int dtype, int M, int N, int K, const void* A, const void* B, const float* bias,

@@ -286,6 +286,44 @@ def attention_hm(q, k, v, scale=None):
     return G.done(out, (B, H, Lq, d), "irx_op_attention_hm")
 
 
+def _inp_at(t, off):
+    """G.inp's copy placed `off` elements into its allocation (an operand that is not 16-byte aligned); the elements
+    in front of it are NaN as well."""
+    if not off or not G.ENABLED:
+        return G.inp(t)
+    span = 1 + sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
+    flat = torch.full((off + span + G.back_elems(t.stride(-2), t.element_size()),), float("nan"), dtype=t.dtype,
+                      device=t.device)
+    g = flat.as_strided(t.shape, t.stride(), off)
+    g.copy_(t)
+    return g
+
+
+def attention_ex(q, k, v, scale, causal=False, q_scaled=False, o_hm=False, ld_pad=0, q_off=0):
+    """The launch as models.cpp makes it (irx_op_attention_ex): q [B,H,Lq,d], k / v [B,H,Lk,d] are strided VIEWS (unit
+    last stride) whose batch, head and row strides go to the kernel as they are — head-major tensors, permuted
+    row-major ones, column slices of a wider buffer (whose other columns are NaN in the guarded copy).  The output is
+    head-major [B,H,Lq,d] (o_hm) or row-major [B,Lq,H d] with ld_pad sentinel columns; returned as a [B,H,Lq,d] view.
+    q_off: q is placed that many elements off its allocation's start."""
+    B, H, Lq, d = q.shape
+    Lk = k.shape[2]
+    assert q.stride(3) == k.stride(3) == v.stride(3) == 1 and k.shape == v.shape
+    if o_hm:
+        o = G.out(q.device, q.dtype, B, H, Lq, d)
+        ldo, so, hso = d, H * Lq * d, Lq * d
+    else:
+        ldo = H * d + ld_pad
+        o = G.Out(q.device, q.dtype, Lq, H * d, ld=ldo, batch=B)
+        so, hso = Lq * ldo, 0
+    q, k, v = _inp_at(q, q_off), G.inp(k), G.inp(v)
+    L.call("irx_op_attention_ex", S(), DT[q.dtype], B, H, Lq, Lk, d, P(q), q.stride(2), q.stride(0), q.stride(1),
+           P(k), k.stride(2), k.stride(0), k.stride(1), P(v), v.stride(2), v.stride(0), v.stride(1), o.ptr(), ldo, so,
+           hso, float(scale), int(causal), int(q_scaled))
+    if o_hm:
+        return G.done(o, (B, H, Lq, d), "irx_op_attention_ex")
+    return o.check("irx_op_attention_ex").unflatten(-1, (H, d)).permute(0, 2, 1, 3)
+
+
 # ------------------------------------------------------------------ elementwise kernels between the GEMMs
 def softmax_rows(x, cols, ldo, dt):
     """x: fp32 [rows][ldi] device tensor of which columns [0, cols) are the scores -> the whole [rows][ldo] output
