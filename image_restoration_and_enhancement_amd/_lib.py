@@ -17,6 +17,7 @@ IRX_MODEL_UNET, IRX_MODEL_VAE, IRX_MODEL_CLIP = 0, 1, 2
 IRX_MODEL_LPIPS = 3       # LPIPS(alex), the reference's src/metrics.py:97-111
 IRX_MODEL_FID = 4         # InceptionV3 pooled features, the reference's src/metrics.py:70-80
 IRX_MODEL_SRVGG = 5       # Real-ESRGAN's SRVGGNetCompact, the reference's src/inference.py:335-336, :579-591
+IRX_MODEL_SAFETY = 6      # StableDiffusionSafetyChecker, run_safety_checker inside src/inference.py:486, :566, :664
 IRX_LAYOUT_VEC, IRX_LAYOUT_MAT, IRX_LAYOUT_CONV, IRX_LAYOUT_EMB = 0, 1, 2, 3
 IRX_LAYOUT_MAT_GEGLU64, IRX_LAYOUT_VEC_GEGLU64 = 4, 5
 IRX_LAYOUT_VEC_LN_U, IRX_LAYOUT_VEC_LN_V = 6, 7
@@ -40,6 +41,8 @@ class ModelConfig(C.Structure):
         ("vocab_size", C.c_int), ("hidden_size", C.c_int), ("intermediate_size", C.c_int),
         ("num_layers", C.c_int), ("max_positions", C.c_int), ("layer_norm_eps", C.c_float),
         ("quick_gelu", C.c_int),
+        ("image_size", C.c_int), ("patch_size", C.c_int), ("projection_dim", C.c_int),
+        ("n_special", C.c_int), ("n_concepts", C.c_int),
     ]
 
 
@@ -152,6 +155,14 @@ _SIGS = {
     "irx_op_srvgg_conv": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "irx_op_srvgg_tail": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irx_op_srvgg_prelu": (i32, [vp, i32, vp, i64, i32, vp, vp]),
+    # SD safety checker: run_safety_checker inside the img2img calls, src/inference.py:486, :566, :664
+    "irx_safety_workspace_bytes": (i32, [vp, i32, C.POINTER(sz)]),
+    "irx_safety_check_u8": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, sz]),
+    "irx_safety_embed_u8": (i32, [vp, vp, vp, i32, vp, vp, vp, sz]),
+    "irx_safety_blank_u8": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "irx_op_safety_patches": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp]),
+    "irx_op_safety_tokens": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, vp]),
+    "irx_op_safety_head": (i32, [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp]),
     "irx_op_conv2d": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32,
                             i32, i32, i32, vp, i64, vp, vp, i32, i32]),
     "irx_op_gemm": (i32, [vp, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, f32, i32, vp, i64, i32, i32, i64,

@@ -38,6 +38,8 @@ PER_FILE = {"elementwise.hip": ["-ffp-contract=off"],
             "fid.hip": ["-ffp-contract=off"],
             # the SRVGG epilogues and tail as srvgg_host.py writes them: slope * v, + bias, + x, * 255 each on its own
             "srvgg.hip": ["-ffp-contract=off"],
+            # the safety checker's decision as numpy writes it: cos - thr, + adj, * 1000 each rounded on its own
+            "safety.hip": ["-ffp-contract=off"],
             # Pillow's coefficient doubles: libm's sin, IEEE divisions, no FMA (csrc/resample_coeffs.cpp)
             "resample_coeffs.cpp": ["-ffp-contract=off", "-fno-fast-math"]}
 

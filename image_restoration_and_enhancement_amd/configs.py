@@ -116,6 +116,97 @@ class CLIPConfig:
 
 
 @dataclass
+class SafetyConfig:
+    """diffusers' StableDiffusionSafetyChecker: `safety_checker/config.json` (its `vision_config` is the CLIP ViT-L/14
+    tower; the defaults restate the file of `sd-legacy/stable-diffusion-v1-5`) and `feature_extractor/
+    preprocessor_config.json` (CLIPImageProcessor).  Only what those two files set in the SD-1.5 snapshot is supported:
+    anything else is a ValueError, never a silent approximation."""
+    hidden_size: int = 1024
+    intermediate_size: int = 4096
+    num_hidden_layers: int = 24
+    num_attention_heads: int = 16
+    patch_size: int = 14
+    image_size: int = 224
+    layer_norm_eps: float = 1e-5
+    hidden_act: str = "quick_gelu"
+    projection_dim: int = 768
+    n_special: int = 3                 # rows of special_care_embeds
+    n_concepts: int = 17               # rows of concept_embeds
+    # CLIPImageProcessor
+    resize_size: int = 224             # the shortest edge after the resize (Pillow BICUBIC)
+    crop_size: int = 224               # the centre crop, square
+    rescale_factor: float = 1 / 255
+    image_mean: List[float] = field(default_factory=lambda: [0.48145466, 0.4578275, 0.40821073])
+    image_std: List[float] = field(default_factory=lambda: [0.26862954, 0.26130258, 0.27577711])
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "SafetyConfig":
+        c = cls()
+        v = d.get("vision_config") or d.get("vision_config_dict") or {}
+        for k in ("hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "patch_size",
+                  "image_size"):
+            if k in v:
+                setattr(c, k, int(v[k]))
+        if "layer_norm_eps" in v:
+            c.layer_norm_eps = float(v["layer_norm_eps"])
+        if "hidden_act" in v:
+            c.hidden_act = str(v["hidden_act"])
+        if "projection_dim" in d:
+            c.projection_dim = int(d["projection_dim"])
+        elif "projection_dim" in v:
+            c.projection_dim = int(v["projection_dim"])
+        if c.hidden_act not in ("quick_gelu", "gelu"):
+            raise ValueError(f"unsupported CLIP activation {c.hidden_act}")
+        if c.image_size % c.patch_size or c.hidden_size % c.num_attention_heads:
+            raise ValueError("safety checker: image_size must be a multiple of patch_size and hidden_size of the heads")
+        c.resize_size = c.crop_size = c.image_size
+        return c
+
+    def from_preprocessor(self, d: dict) -> "SafetyConfig":
+        """The same config with `preprocessor_config.json` read into it: both the old form (`"size": 224,
+        "crop_size": 224`) and the new one (`{"shortest_edge": 224}`, `{"height": 224, "width": 224}`)."""
+        for k in ("do_resize", "do_center_crop", "do_normalize", "do_rescale"):
+            if not d.get(k, True):
+                raise ValueError(f"safety checker preprocessor: {k} = false is unsupported")
+        if int(d.get("resample", 3)) != 3:
+            raise ValueError(f"safety checker preprocessor: resample {d.get('resample')} is unsupported (3, BICUBIC)")
+        size = d.get("size", self.resize_size)
+        if isinstance(size, dict):
+            if set(size) != {"shortest_edge"}:
+                raise ValueError(f"safety checker preprocessor: size {size} is unsupported (shortest_edge)")
+            size = size["shortest_edge"]
+        crop = d.get("crop_size", self.crop_size)
+        if isinstance(crop, dict):
+            if set(crop) != {"height", "width"} or crop["height"] != crop["width"]:
+                raise ValueError(f"safety checker preprocessor: crop_size {crop} is unsupported (a square)")
+            crop = crop["height"]
+        if int(crop) != self.image_size:
+            raise ValueError(f"safety checker preprocessor: crop_size {crop} is not the tower's image_size "
+                             f"{self.image_size}")
+        if int(size) < int(crop):
+            raise ValueError(f"safety checker preprocessor: size {size} below crop_size {crop} (the crop would pad)")
+        self.resize_size, self.crop_size = int(size), int(crop)
+        if "rescale_factor" in d:
+            self.rescale_factor = float(d["rescale_factor"])
+        for k in ("image_mean", "image_std"):
+            if k in d:
+                val = [float(x) for x in d[k]]
+                if len(val) != 3:
+                    raise ValueError(f"safety checker preprocessor: {k} must have three entries")
+                setattr(self, k, val)
+        return self
+
+    @classmethod
+    def from_dir(cls, checker_dir: str | Path, preprocessor_dir: str | Path | None = None) -> "SafetyConfig":
+        """`<checker_dir>/config.json`, and `preprocessor_config.json` from `preprocessor_dir` (default: the
+        `feature_extractor/` directory next to `checker_dir`) when that file exists."""
+        p = Path(checker_dir)
+        c = cls.from_dict(json.loads((p / "config.json").read_text()))
+        f = (Path(preprocessor_dir) if preprocessor_dir else p.parent / "feature_extractor") / "preprocessor_config.json"
+        return c.from_preprocessor(json.loads(f.read_text())) if f.exists() else c
+
+
+@dataclass
 class SchedulerConfig:
     kind: str = "pndm"                 # "pndm" (denoise/sr/colorize) | "ddim" (inpaint)
     num_train_timesteps: int = 1000

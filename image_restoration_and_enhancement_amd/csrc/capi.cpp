@@ -234,6 +234,7 @@ int irx_model_create(int kind, const irx_model_config* cfg, int dtype, irx_model
     else if (kind == IRX_MODEL_LPIPS) h->m.reset(new LpipsAlex(*cfg, dtype));
     else if (kind == IRX_MODEL_FID) h->m.reset(new InceptionFid(*cfg, dtype));
     else if (kind == IRX_MODEL_SRVGG) h->m.reset(new Srvgg(*cfg, dtype));
+    else if (kind == IRX_MODEL_SAFETY) h->m.reset(new SafetyChecker(*cfg, dtype));
     else throw Error("unknown model kind");
   } catch (...) {
     delete h;
@@ -752,6 +753,60 @@ int irx_srvgg_u8(irx_model* m, void* s, const uint8_t* in_u8, int B, int H, int 
   as<Srvgg>(m, IRX_MODEL_SRVGG)->enhance(S(s), in_u8, B, H, W, in_lut, out_u8, out_f, (char*)ws, ws_bytes);
   IRX_API_END
 }
+// ------------------------------------------------------------------ SD safety checker (safety_model.cpp, safety.hip;
+// StableDiffusionImg2ImgPipeline.run_safety_checker inside the calls at src/inference.py:486, :566, :664)
+int irx_safety_workspace_bytes(const irx_model* m, int B, size_t* bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(bytes, "null argument");
+  *bytes = const_cast<SafetyChecker*>(as<SafetyChecker>(m, IRX_MODEL_SAFETY))->workspace_bytes(B);
+  IRX_API_END
+}
+int irx_safety_check_u8(irx_model* m, void* s, const uint8_t* crop_u8, int B, const float* in_lut, float* scores,
+                        int* flags, void* ws, size_t ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(crop_u8 && in_lut && scores && flags && ws, "null argument");
+  as<SafetyChecker>(m, IRX_MODEL_SAFETY)->check(S(s), crop_u8, B, in_lut, scores, flags, nullptr, (char*)ws, ws_bytes);
+  IRX_API_END
+}
+int irx_safety_embed_u8(irx_model* m, void* s, const uint8_t* crop_u8, int B, const float* in_lut, float* embeds,
+                        void* ws, size_t ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(crop_u8 && in_lut && embeds && ws, "null argument");
+  as<SafetyChecker>(m, IRX_MODEL_SAFETY)->check(S(s), crop_u8, B, in_lut, nullptr, nullptr, embeds, (char*)ws, ws_bytes);
+  IRX_API_END
+}
+int irx_safety_blank_u8(void* s, uint8_t* img, float* f01, int B, int H, int W, const int* flags) {
+  IRX_API_BEGIN
+  IRX_CHECK(img && flags, "null argument");
+  IRX_CHECK(H > 0 && W > 0, "safety blank: H and W must be positive");
+  safety_blank(img, f01, B, (long)H * W * 3, flags, S(s));
+  IRX_API_END
+}
+int irx_op_safety_patches(void* s, int dtype, const uint8_t* crop_u8, int B, int Sd, int patch, int kpad,
+                          const float* in_lut, void* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(crop_u8 && in_lut && out, "null argument");
+  IRX_CHECK(dtype == IRX_F32 || dtype == IRX_BF16 || dtype == IRX_F16, "dtype must be IRX_F32, IRX_BF16 or IRX_F16");
+  safety_patches(dtype, crop_u8, B, Sd, patch, kpad, in_lut, out, S(s));
+  IRX_API_END
+}
+int irx_op_safety_tokens(void* s, int dtype, const void* patch_out, const float* cls, const void* pos, int B, int P,
+                         int D, void* out) {
+  IRX_API_BEGIN
+  IRX_CHECK(patch_out && cls && pos && out, "null argument");
+  IRX_CHECK(dtype == IRX_F32 || dtype == IRX_BF16 || dtype == IRX_F16, "dtype must be IRX_F32, IRX_BF16 or IRX_F16");
+  safety_tokens(dtype, patch_out, cls, pos, B, P, D, out, S(s));
+  IRX_API_END
+}
+int irx_op_safety_head(void* s, const float* embeds, int B, int n, const float* special, int ns, const float* concepts,
+                       int nc, const float* thr_special, const float* thr_concepts, float* scores, int* flags) {
+  IRX_API_BEGIN
+  IRX_CHECK(embeds && concepts && thr_concepts && scores && flags, "null argument");
+  IRX_CHECK(ns == 0 || (special && thr_special), "null argument");
+  safety_head(embeds, B, n, special, ns, concepts, nc, thr_special, thr_concepts, scores, flags, S(s));
+  IRX_API_END
+}
+
 static void srvgg_op_shape(int B, int H, int W) {
   IRX_CHECK(B > 0 && H > 0 && W > 0, "batch and sizes must be positive");
   IRX_CHECK((long)B * H * W * 64 <= 0x7fffffffL, "batch x image too large for one call");

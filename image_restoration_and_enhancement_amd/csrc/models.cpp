@@ -1155,25 +1155,50 @@ void Vae::decode(hipStream_t s, const void* z, int B, int h, int w, void* out, c
 }
 
 // ---------------------------------------------------------------------------------------------- CLIP
+Model::ClipLayerW Model::make_clip_layer(const std::string& b, int D, int F) {
+  const std::string s = b + "self_attn.";
+  ClipLayerW l;
+  l.ln1w = vec(b + "layer_norm1.weight", D); l.ln1b = vec(b + "layer_norm1.bias", D);
+  l.qkvw = mat(s + "q_proj.weight|" + s + "k_proj.weight|" + s + "v_proj.weight", 3 * D, D);
+  l.qkvb = vec(s + "q_proj.bias|" + s + "k_proj.bias|" + s + "v_proj.bias", 3 * D);
+  l.ow = mat(s + "out_proj.weight", D, D); l.ob = vec(s + "out_proj.bias", D);
+  l.ln2w = vec(b + "layer_norm2.weight", D); l.ln2b = vec(b + "layer_norm2.bias", D);
+  l.f1w = mat(b + "mlp.fc1.weight", F, D); l.f1b = vec(b + "mlp.fc1.bias", F);
+  l.f2w = mat(b + "mlp.fc2.weight", D, F); l.f2b = vec(b + "mlp.fc2.bias", D);
+  return l;
+}
+
+void Model::clip_layer(Ctx& c, const ClipLayerW& l, void* h, int B, int L, int D, int F, int H, float eps, int act,
+                       int causal, int imgs, const ClipScratch& t) {
+  const long M = (long)B * L;
+  const size_t es = dsize(dt_);
+  lnorm(c, h, M, D, l.ln1w, l.ln1b, eps, t.n);
+  linear(c, t.n, D, M, D, l.qkvw, 3 * D, fptr(l.qkvb), t.qkv, 3 * D, ACT_NONE, nullptr, 0, 0, imgs);
+  if (!c.ws->dry()) {
+    AttnArgs aa;
+    aa.dtype = dt_; aa.B = B; aa.H = H; aa.Lq = L; aa.Lk = L; aa.d = D / H;
+    aa.scale = 1.0f / std::sqrt((float)(D / H));
+    aa.causal = causal;
+    aa.q = t.qkv; aa.ldq = 3 * D; aa.sq = (long)L * 3 * D;
+    aa.k = (char*)t.qkv + D * es; aa.ldk = 3 * D; aa.sk = aa.sq;
+    aa.v = (char*)t.qkv + 2 * D * es; aa.ldv = 3 * D; aa.sv = aa.sq;
+    aa.o = t.att; aa.ldo = D; aa.so = (long)L * D;
+    attention(aa, c.s);
+  }
+  linear(c, t.att, D, M, D, l.ow, D, fptr(l.ob), h, D, ACT_NONE, h, D, 0, imgs);
+  lnorm(c, h, M, D, l.ln2w, l.ln2b, eps, t.n);
+  linear(c, t.n, D, M, D, l.f1w, F, fptr(l.f1b), t.f, F, act, nullptr, 0, 0, imgs);
+  linear(c, t.f, F, M, F, l.f2w, D, fptr(l.f2b), h, D, ACT_NONE, h, D, 0, imgs);
+}
+
 Clip::Clip(const irx_model_config& cfg, int dtype) : Model(IRX_MODEL_CLIP, cfg, dtype) {
   const int D = cfg.hidden_size, F = cfg.intermediate_size;
   IRX_CHECK(D > 0 && F > 0 && cfg.num_layers > 0 && D % cfg.heads == 0, "bad CLIP config");
   const std::string p = "text_model.";
   tok = reg(p + "embeddings.token_embedding.weight", IRX_LAYOUT_EMB, dt_, {cfg.vocab_size, D});
   pos = reg(p + "embeddings.position_embedding.weight", IRX_LAYOUT_EMB, dt_, {cfg.max_positions, D});
-  for (int i = 0; i < cfg.num_layers; ++i) {
-    const std::string b = p + "encoder.layers." + std::to_string(i) + ".";
-    const std::string s = b + "self_attn.";
-    Layer l;
-    l.ln1w = vec(b + "layer_norm1.weight", D); l.ln1b = vec(b + "layer_norm1.bias", D);
-    l.qkvw = mat(s + "q_proj.weight|" + s + "k_proj.weight|" + s + "v_proj.weight", 3 * D, D);
-    l.qkvb = vec(s + "q_proj.bias|" + s + "k_proj.bias|" + s + "v_proj.bias", 3 * D);
-    l.ow = mat(s + "out_proj.weight", D, D); l.ob = vec(s + "out_proj.bias", D);
-    l.ln2w = vec(b + "layer_norm2.weight", D); l.ln2b = vec(b + "layer_norm2.bias", D);
-    l.f1w = mat(b + "mlp.fc1.weight", F, D); l.f1b = vec(b + "mlp.fc1.bias", F);
-    l.f2w = mat(b + "mlp.fc2.weight", D, F); l.f2b = vec(b + "mlp.fc2.bias", D);
-    layers_.push_back(l);
-  }
+  for (int i = 0; i < cfg.num_layers; ++i)
+    layers_.push_back(make_clip_layer(p + "encoder.layers." + std::to_string(i) + ".", D, F));
   fw = vec(p + "final_layer_norm.weight", D); fb = vec(p + "final_layer_norm.bias", D);
 }
 
@@ -1188,25 +1213,10 @@ void Clip::run(Ctx& c, const int* ids, int B, int L, void* out) {
   void* att = c.ws->alloc(M * D * es);
   void* f = c.ws->alloc(M * F * es);
   if (!c.ws->dry()) embed_tokens(dt_, ids, B, L, ptr(tok), ptr(pos), D, h, c.s);
-  for (auto& l : layers_) {
-    lnorm(c, h, M, D, l.ln1w, l.ln1b, eps, n);
-    linear(c, n, D, M, D, l.qkvw, 3 * D, fptr(l.qkvb), qkv, 3 * D);
-    if (!c.ws->dry()) {
-      AttnArgs aa;
-      aa.dtype = dt_; aa.B = B; aa.H = H; aa.Lq = L; aa.Lk = L; aa.d = D / H;
-      aa.scale = 1.0f / std::sqrt((float)(D / H));
-      aa.causal = 1;
-      aa.q = qkv; aa.ldq = 3 * D; aa.sq = (long)L * 3 * D;
-      aa.k = (char*)qkv + D * es; aa.ldk = 3 * D; aa.sk = aa.sq;
-      aa.v = (char*)qkv + 2 * D * es; aa.ldv = 3 * D; aa.sv = aa.sq;
-      aa.o = att; aa.ldo = D; aa.so = (long)L * D;
-      attention(aa, c.s);
-    }
-    linear(c, att, D, M, D, l.ow, D, fptr(l.ob), h, D, ACT_NONE, h, D);
-    lnorm(c, h, M, D, l.ln2w, l.ln2b, eps, n);
-    linear(c, n, D, M, D, l.f1w, F, fptr(l.f1b), f, F, cfg_.quick_gelu ? ACT_QUICK_GELU : ACT_GELU);
-    linear(c, f, F, M, F, l.f2w, D, fptr(l.f2b), h, D, ACT_NONE, h, D);
-  }
+  ClipScratch t;
+  t.n = n; t.qkv = qkv; t.att = att; t.f = f;
+  for (auto& l : layers_)
+    clip_layer(c, l, h, B, L, D, F, H, eps, cfg_.quick_gelu ? ACT_QUICK_GELU : ACT_GELU, 1, 0, t);
   lnorm(c, h, M, D, fw, fb, eps, out);
   c.ws->free(f);
   c.ws->free(att);

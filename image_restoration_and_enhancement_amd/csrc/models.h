@@ -1,5 +1,5 @@
 // irx — native model graphs (UNet2DConditionModel, AutoencoderKL, CLIPTextModel, LPIPS AlexNet, FID InceptionV3,
-// Real-ESRGAN SRVGGNetCompact) over the irx kernels.
+// Real-ESRGAN SRVGGNetCompact, StableDiffusionSafetyChecker) over the irx kernels.
 #pragma once
 #include <map>
 #include <memory>
@@ -114,6 +114,15 @@ class Model {
   P up2_weights(const std::string& name, int ch);   // IRX_LAYOUT_CONV_UP2 entry (16-bit engines; unset for fp32)
   // GroupNorm + SiLU + 3x3 conv to a narrow output head in one kernel (gn_conv_narrow); false: not taken
   bool gn_conv_out(Ctx& c, const Act& x, P g, P gb, float eps, P w, P b, int cout, void* out, int ldo, int out_f32);
+  // one pre-LN CLIP encoder layer (transformers CLIPEncoderLayer; fused q|k|v): the text model's with the causal mask,
+  // the safety checker's vision tower without.  make_clip_layer registers `<b>layer_norm1 ... mlp.fc2` in that order;
+  // clip_layer updates the residual stream h [B][L][D] in place through the caller's scratch (n, att [M][D], qkv
+  // [M][3D], f [M][F]); imgs: the images the rows span (GemmArgs::imgs; 0: not image-indexed)
+  struct ClipLayerW { P ln1w, ln1b, qkvw, qkvb, ow, ob, ln2w, ln2b, f1w, f1b, f2w, f2b; };
+  struct ClipScratch { void *n = nullptr, *qkv = nullptr, *att = nullptr, *f = nullptr; };
+  ClipLayerW make_clip_layer(const std::string& b, int D, int F);
+  void clip_layer(Ctx& c, const ClipLayerW& l, void* h, int B, int L, int D, int F, int H, float eps, int act,
+                  int causal, int imgs, const ClipScratch& t);
 
   int kind_;
   irx_model_config cfg_;
@@ -240,10 +249,35 @@ class Clip : public Model {
   void encode(hipStream_t s, const int* ids, int B, int L, void* out, char* ws, size_t cap);
 
  private:
-  struct Layer { P ln1w, ln1b, qkvw, qkvb, ow, ob, ln2w, ln2b, f1w, f1b, f2w, f2b; };
   void run(Ctx& c, const int* ids, int B, int L, void* out);
   P tok, pos, fw, fb;
-  std::vector<Layer> layers_;
+  std::vector<ClipLayerW> layers_;
+};
+
+// diffusers' StableDiffusionSafetyChecker (safety_host.py; run_safety_checker at the end of the reference's img2img
+// calls, src/inference.py:486, :566, :664): the CLIP vision tower (`vision_model.vision_model.*`: a bias-free patch conv
+// as a GEMM over safety_patches' rows, class + position embeddings, pre_layrnorm, cfg.num_layers encoder layers without
+// a mask, post_layernorm of token 0), `visual_projection`, and the cosine head of safety.hip against the blob's
+// `special_care_embeds` / `concept_embeds` (fp32; packed as given: safety_gpu normalises them on the host) and their
+// `*_weights` thresholds.  The tower runs in the model dtype, the projection's output and the head in fp32.  Every
+// GEMM is planned for the canonical batch and the head is per image: an image's scores do not depend on the batch.
+class SafetyChecker : public Model {
+ public:
+  SafetyChecker(const irx_model_config& cfg, int dtype);
+  static constexpr int kMaxBatch = 64;   // per call (above it the small-M plans of the pooled rows would change)
+  int side() const { return cfg_.image_size; }
+  int rows() const { return cfg_.n_special + cfg_.n_concepts; }
+  size_t workspace_bytes(int B);
+  // crop uint8 [B][S][S][3]; lut float[256][3]; scores fp32 [B][n_special + n_concepts]; flags int [B]; embeds (or
+  // null) fp32 [B][projection_dim], the image embeddings the head reads
+  void check(hipStream_t s, const uint8_t* crop, int B, const float* lut, float* scores, int* flags, float* embeds,
+             char* ws, size_t cap);
+
+ private:
+  void run(Ctx& c, const uint8_t* crop, int B, const float* lut, float* scores, int* flags, float* embeds);
+  int kpad_ = 0;
+  P patch_w, cls, pos, pre_w, pre_b, post_w, post_b, proj_w, sp_e, co_e, sp_t, co_t;
+  std::vector<ClipLayerW> layers_;
 };
 
 // LPIPS(alex) v0.1, eval mode, spatial = false (lpips_host.py; the reference's src/metrics.py:97-111): the AlexNet

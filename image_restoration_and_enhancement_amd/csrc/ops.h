@@ -426,4 +426,20 @@ void srvgg_prelu(int dtype, const void* x, long rows, int C, const float* slope,
 void srvgg_shuffle_add(int dtype, const void* conv, const uint8_t* img, int B, int H, int W, const float* lut,
                        uint8_t* out_u8, float* out_f, hipStream_t s);
 
+// ------------------------------------------------------------ SD safety checker (safety.hip; SafetyChecker, models.h)
+// uint8 [B][S][S][3] (resized, cropped) -> patch rows [B * (S / pz)^2][Kpad] of `dtype` through lut float[256][3]
+// (safety_host.input_table); column k = (c * pz + ky) * pz + kx, columns [3 pz pz, Kpad) zero
+void safety_patches(int dtype, const uint8_t* img, int B, int S, int pz, int Kpad, const float* lut, void* out,
+                    hipStream_t s);
+// out[b][0] = cls + pos[0], out[b][1 + p] = patch[b][p] + pos[1 + p]; patch [B][P][D], pos [P + 1][D] and out
+// [B][P + 1][D] of `dtype`, cls fp32 [D] (rounded to `dtype` when read)
+void safety_tokens(int dtype, const void* patch, const float* cls, const void* pos, int B, int P, int D, void* out,
+                   hipStream_t s);
+// emb fp32 [B][n]; special [ns][n] / conc [nc][n] fp32 unit rows; the thresholds fp32 [ns] / [nc] -> scores
+// [B][ns + nc] (the cosines, special rows first) and flags int [B]; n <= 4096, ns + nc <= 64
+void safety_head(const float* emb, int B, int n, const float* special, int ns, const float* conc, int nc,
+                 const float* thr_special, const float* thr_concept, float* scores, int* flags, hipStream_t s);
+// img[b][0, n) = 0 (and f01[b][0, n), if not null) for every b with flags[b] != 0
+void safety_blank(uint8_t* img, float* f01, int B, long n, const int* flags, hipStream_t s);
+
 }  // namespace irx

@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .configs import UNetConfig, VAEConfig, CLIPConfig
+from .configs import UNetConfig, VAEConfig, CLIPConfig, SafetyConfig
 
 DTYPES = {"fp32": L.IRX_F32, "float32": L.IRX_F32, "bf16": L.IRX_BF16, "bfloat16": L.IRX_BF16,
           "fp16": L.IRX_F16, "float16": L.IRX_F16, "half": L.IRX_F16}
@@ -63,6 +63,14 @@ def model_config(kind: int, cfg) -> L.ModelConfig:
         c.norm_groups = cfg.norm_num_groups
         c.norm_eps = cfg.norm_eps
         c.heads = 1
+    elif kind == L.IRX_MODEL_SAFETY:
+        assert isinstance(cfg, SafetyConfig)
+        c.hidden_size, c.intermediate_size, c.num_layers = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
+        c.heads = cfg.num_attention_heads
+        c.layer_norm_eps = cfg.layer_norm_eps
+        c.quick_gelu = int(cfg.hidden_act == "quick_gelu")
+        c.image_size, c.patch_size, c.projection_dim = cfg.image_size, cfg.patch_size, cfg.projection_dim
+        c.n_special, c.n_concepts = cfg.n_special, cfg.n_concepts
     else:
         assert isinstance(cfg, CLIPConfig)
         c.vocab_size, c.hidden_size, c.intermediate_size = cfg.vocab_size, cfg.hidden_size, cfg.intermediate_size

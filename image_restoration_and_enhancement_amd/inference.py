@@ -26,6 +26,11 @@ Differences that follow from the engine (documented in INTEGRATION.md):
   (`fine_tuned_dir == "nonexistent"`), from a local Hugging Face cache snapshot of `pretrained_id` (no
   network).  `config[task]["weights"] = "random"` selects seeded random weights (benchmarks / tests).
 * tasks that resolve to the same weights (denoise / sr / colorize in pretrained mode) share one engine.
+* the img2img tasks end with the Stable Diffusion safety checker where the reference's pipelines carry one
+  (`run_safety_checker`; pretrained mode: the snapshot's `model_index.json` lists it; the fine-tuned `best/`
+  directories list `[null, null]`): `config["engine"]["safety_checker"]` = "auto" (default), False, or a
+  `safety_checker/` directory to use for every img2img task; IRX_SAFETY_CHECKER means the same when the key is absent.
+  A flagged image comes back black and diffusers' warning is logged.  Inpainting is never filtered, as in the reference.
 * Real-ESRGAN (`default_backend` "realesrgan", or "auto" after a failed SD load) runs the compact network the
   reference constructs (src/inference.py:335-336) from a weight file the user names: `config["sr"]
   ["realesrgan_weights"]` or the environment variable IRX_REALESRGAN_WEIGHTS (a file, or a directory holding one
@@ -65,6 +70,12 @@ SD_PARAMS = {
     "inpaint": (0.6, 30, 5.0),       # :758-767
 }
 INPAINT_SIZE = 512                   # unet.sample_size (64) x vae scale factor (8)
+
+
+class SafetyCheckerError(IrxError):
+    """A safety checker the configuration names cannot be loaded (unreadable directory, keys that do not fit).  Like a
+    missing native library it is never hidden behind a fallback: the user asked for a filter, so no unfiltered or
+    classical result is returned in its place."""
 
 
 class NativeSDModel:
@@ -160,6 +171,13 @@ class RestorationPipeline:
             "inpaint": "high quality detailed photo",
         }
         self._engines: Dict[tuple, object] = {}
+        # config["engine"]["safety_checker"]: "auto" | False | a safety_checker/ directory (IRX_SAFETY_CHECKER when absent)
+        self.safety_setting = engine_cfg.get("safety_checker", os.environ.get("IRX_SAFETY_CHECKER") or "auto")
+        if self.safety_setting is None or self.safety_setting is True:
+            self.safety_setting = "auto"
+        self._checkers: Dict[tuple, object] = {}
+        self._warned_unfiltered: set = set()
+        self.last_nsfw: Optional[List[Optional[bool]]] = None    # per image of the last img2img call / restore_batch
 
     # ------------------------------------------------------------------------------------ loading
     def _model_source(self, task: str, cfg: dict, train_script: str) -> str:
@@ -176,6 +194,49 @@ class RestorationPipeline:
             return str(_resolve_pretrained(cfg["pretrained_id"]))
         raise FileNotFoundError(f"Fine-tuned {task} model not found at {p}. "
                                 f"Please train the model first with: python3 scripts/{train_script}")
+
+    def _safety_dir(self, task: str, source: str) -> Optional[str]:
+        """The `safety_checker/` directory whose checker filters `task` served from `source`, or None.  Inpainting
+        never has one (the reference switches it off, src/inference.py:444-451, :746-752).  "auto": the checker the
+        model directory's `model_index.json` lists, when its config and a weight file are there; listed without its
+        files, diffusers would fail the whole load and the reference land on its classical fallback — here the task
+        runs unfiltered, as before, and says so once."""
+        from . import safety_host
+        setting = self.safety_setting
+        if task == "inpaint" or setting is False or str(setting).lower() in ("false", "0", "off", "none"):
+            return None
+        if setting != "auto":
+            return str(setting)
+        if source == "random" or not safety_host.listed_in_model_index(source):
+            return None
+        d = Path(source) / "safety_checker"
+        if (d / "config.json").is_file() and safety_host.weight_file(d) is not None:
+            return str(d)
+        if source not in self._warned_unfiltered:
+            self._warned_unfiltered.add(source)
+            logger.warning(f"{source}/model_index.json lists a safety checker but {d} has no config.json or weight "
+                           "file: outputs are not filtered")
+        return None
+
+    def _load_checker(self, path: str):
+        """The native checker of a `safety_checker/` directory in the engine dtype (tests stub this)."""
+        from . import safety_gpu
+        return safety_gpu.SafetyChecker(path, self.engine_dtype, self.device)
+
+    def _checker(self, task: str, source: str):
+        path = self._safety_dir(task, source)
+        if path is None:
+            return None
+        key = (path, self.engine_dtype)
+        if key not in self._checkers:
+            try:
+                self._checkers[key] = self._load_checker(path)
+            except IrxError:
+                raise
+            except Exception as e:
+                raise SafetyCheckerError(f"safety checker {path}: {e}") from e
+            logger.info(f"safety checker ready ({path}, {self.engine_dtype})")
+        return self._checkers[key]
 
     def _load_native(self, task: str, source: str) -> NativeSDModel:
         if not self.device.startswith("cuda"):
@@ -194,7 +255,10 @@ class RestorationPipeline:
                 eng = SDEngine(pc, self.engine_dtype, self.device, weights=source, vae_dtype=self.vae_dtype)
             self._engines[key] = eng
             logger.info(f"{task} engine ready ({source}, {self.engine_dtype}, VAE {self.vae_dtype})")
-        return NativeSDModel(self._engines[key], kind, source)
+        eng = self._engines[key]
+        if kind == "img2img":      # (on every load: a cached engine follows the current setting)
+            eng.safety = self._checker(task, source)
+        return NativeSDModel(eng, kind, source)
 
     def _try_load(self, task: str, train_script: str) -> NativeSDModel:
         cfg = self.config[task]
@@ -288,7 +352,14 @@ class RestorationPipeline:
         if dev.shape[1] < 8 or dev.shape[2] < 8:
             raise ValueError(f"image too small for the VAE: {images[0].size}")
         res = model.engine.img2img(dev, prompt, strength, steps, guidance, seed=self.seed)
-        return [Image.fromarray(a) for a in res.images_u8.cpu().numpy()]
+        out = [Image.fromarray(a) for a in res.images_u8.cpu().numpy()]
+        # the flags come back with the image (flagged rows are already black on the device)
+        nsfw = getattr(res, "nsfw", None)
+        self.last_nsfw = [None] * len(out) if nsfw is None else [bool(f) for f in nsfw.cpu().numpy()]
+        if any(self.last_nsfw):
+            from .safety_host import NSFW_WARNING
+            logger.warning(NSFW_WARNING)
+        return out
 
     def _inpaint_native(self, model: NativeSDModel, images: Sequence[Image.Image], masks: Sequence[Image.Image],
                         prompt: str, strength: float, steps: int, guidance: float) -> List[Image.Image]:
@@ -572,6 +643,7 @@ class RestorationPipeline:
         if not isinstance(model, NativeSDModel):
             return [single(im, mk) for im, mk in zip(images, masks)]
         out: List[Optional[Image.Image]] = [None] * len(images)
+        nsfw: List[Optional[bool]] = [None] * len(images)
         groups: Dict[tuple, List[int]] = {}
         prepared = {}
         for i, (im, mk) in enumerate(zip(images, masks)):
@@ -601,6 +673,8 @@ class RestorationPipeline:
                         res = self._inpaint_native(model, ims, [prepared[i][1] for i in chunk], p, s, steps, g)
                     else:
                         res = self._img2img(model, ims, p, s, steps, g)
+                        for i, f in zip(chunk, self.last_nsfw or []):
+                            nsfw[i] = f
                 except IrxError:
                     raise
                 except Exception as e:     # as the single-image entry points: log, then their fallbacks
@@ -608,4 +682,5 @@ class RestorationPipeline:
                     res = [single(images[i], masks[i]) for i in chunk]
                 for i, r in zip(chunk, res):
                     out[i] = r
+        self.last_nsfw = nsfw      # per input image: True = returned black, None = not filtered
         return out  # type: ignore[return-value]

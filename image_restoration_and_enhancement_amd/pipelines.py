@@ -40,6 +40,9 @@ class BatchResult:
     decoded01: Optional[torch.Tensor]       # [B, H, W, 3] fp32 in [0, 1] before rounding (device) or None
     latents: torch.Tensor                   # [B, h, w, 4] fp32 final latents (device)
     timesteps: List[int]
+    # has_nsfw_concept of the safety checker, int32 [B] on the device (flagged rows of images_u8 / decoded01 are
+    # zeros); None: no checker ran (none configured, or inpainting, which the reference never filters)
+    nsfw: Optional[torch.Tensor] = None
 
 
 def _stream():
@@ -93,9 +96,13 @@ class SDEngine:
     """The three native models of one task directory + the batched denoising loop."""
 
     def __init__(self, cfg: PipelineConfig, dtype="bf16", device="cuda", weights="random", weight_seed: int = 0,
-                 state_dicts: Optional[Dict[str, Dict[str, torch.Tensor]]] = None, vae_dtype=None, clip_dtype=None):
+                 state_dicts: Optional[Dict[str, Dict[str, torch.Tensor]]] = None, vae_dtype=None, clip_dtype=None,
+                 safety=None):
         """`dtype` is the UNet's compute type (and the default of the other two models); `vae_dtype` /
-        `clip_dtype` override it per model (e.g. a bf16 UNet with an fp16 VAE)."""
+        `clip_dtype` override it per model (e.g. a bf16 UNet with an fp16 VAE).  `safety`: a
+        `safety_gpu.SafetyChecker` that `img2img` runs on its decoded batch (run_safety_checker of the reference's
+        img2img calls, src/inference.py:486, :566, :664); `inpaint` never runs it (:444-451, :746-752)."""
+        self.safety = safety
         self.cfg = cfg
         self.dt = dtype_code(dtype)
         self.tdt = TORCH_DT[self.dt]
@@ -322,7 +329,8 @@ class SDEngine:
         lat = self.sample_latents(mom, eps1, nz, a, b)
         lat = self.denoise_loop(lat, kv, plans, guidance, cfg_on)
         u8o, f01 = self.decode(lat, want_float)
-        return BatchResult(u8o, f01, lat, [p.t for p in plans])
+        nsfw = self.safety.apply(u8o, f01) if self.safety is not None else None
+        return BatchResult(u8o, f01, lat, [p.t for p in plans], nsfw)
 
     def inpaint(self, u8: torch.Tensor, mask01: torch.Tensor, prompt: str, strength: float, steps: int,
                 guidance: float, seed: int = 42, want_float: bool = False,

@@ -23,7 +23,7 @@ from typing import Dict, Iterator, List, Tuple
 
 import torch
 
-from .configs import UNetConfig, VAEConfig, CLIPConfig
+from .configs import UNetConfig, VAEConfig, CLIPConfig, SafetyConfig
 
 Spec = Tuple[str, Tuple[int, ...]]
 
@@ -187,8 +187,37 @@ def clip_param_specs(cfg: CLIPConfig) -> List[Spec]:
     return s
 
 
+def safety_param_specs(cfg: SafetyConfig) -> List[Spec]:
+    """diffusers' StableDiffusionSafetyChecker under the checkpoint's names (`safety_checker/model.safetensors`): the
+    CLIP vision tower, the projection, and the concept embeddings with their thresholds.  `position_ids` buffers are
+    not parameters and are ignored."""
+    d, f, pz = cfg.hidden_size, cfg.intermediate_size, cfg.patch_size
+    p = "vision_model.vision_model."
+    n_pos = (cfg.image_size // pz) ** 2 + 1
+    s: List[Spec] = [(p + "embeddings.class_embedding", (d,)),
+                     (p + "embeddings.patch_embedding.weight", (d, 3, pz, pz)),
+                     (p + "embeddings.position_embedding.weight", (n_pos, d)),
+                     (p + "pre_layrnorm.weight", (d,)), (p + "pre_layrnorm.bias", (d,))]
+    for i in range(cfg.num_hidden_layers):
+        b = f"{p}encoder.layers.{i}."
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            s += [(b + f"self_attn.{n}.weight", (d, d)), (b + f"self_attn.{n}.bias", (d,))]
+        s += [(b + "layer_norm1.weight", (d,)), (b + "layer_norm1.bias", (d,)),
+              (b + "mlp.fc1.weight", (f, d)), (b + "mlp.fc1.bias", (f,)),
+              (b + "mlp.fc2.weight", (d, f)), (b + "mlp.fc2.bias", (d,)),
+              (b + "layer_norm2.weight", (d,)), (b + "layer_norm2.bias", (d,))]
+    s += [(p + "post_layernorm.weight", (d,)), (p + "post_layernorm.bias", (d,)),
+          ("visual_projection.weight", (cfg.projection_dim, d)),
+          ("concept_embeds", (cfg.n_concepts, cfg.projection_dim)),
+          ("special_care_embeds", (cfg.n_special, cfg.projection_dim)),
+          ("concept_embeds_weights", (cfg.n_concepts,)),
+          ("special_care_embeds_weights", (cfg.n_special,))]
+    return s
+
+
 def param_specs(kind: str, cfg) -> List[Spec]:
-    return {"unet": unet_param_specs, "vae": vae_param_specs, "clip": clip_param_specs}[kind](cfg)
+    return {"unet": unet_param_specs, "vae": vae_param_specs, "clip": clip_param_specs,
+            "safety": safety_param_specs}[kind](cfg)
 
 
 # --------------------------------------------------------------------------- random init
@@ -203,6 +232,10 @@ def random_param(name: str, shape: Tuple[int, ...], fan_in: int, seed: int) -> t
     g = torch.Generator().manual_seed((seed * 1000003 + zlib.crc32(name.encode())) & 0x7FFFFFFFFFFF)
     if "embedding" in name:
         return torch.randn(shape, generator=g) * 0.02
+    if name.endswith("_embeds"):               # the safety checker's concept rows: any direction, any length
+        return torch.randn(shape, generator=g)
+    if name.endswith("_embeds_weights"):       # ... and its thresholds, cosines
+        return torch.rand(shape, generator=g) * 0.2 + 0.1
     u = torch.rand(shape, generator=g) * 2.0 - 1.0
     if _is_norm(name):
         # GroupNorm/LayerNorm affine: near identity, but not exactly, so parity tests see it.

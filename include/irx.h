@@ -34,6 +34,10 @@ extern "C" {
 /* Real-ESRGAN's SRVGGNetCompact(3, 3, 64, 32, upscale 4, prelu) (src/inference.py:335-336): IRX_F16 (the product, the
  * reference's half on a GPU) or IRX_F32 (parity); IRX_BF16 is refused at creation; the config is not read */
 #define IRX_MODEL_SRVGG 5
+/* diffusers' StableDiffusionSafetyChecker (run_safety_checker at the end of the img2img calls, src/inference.py:486,
+ * :566, :664): the CLIP vision tower in the model dtype, the cosine head in fp32.  Reads hidden_size, intermediate_size,
+ * num_layers, heads, layer_norm_eps, quick_gelu and the five safety fields at the end of irx_model_config */
+#define IRX_MODEL_SAFETY 6
 
 /* weight layouts of manifest entries (how the host packs diffusers tensors into the blob) */
 #define IRX_LAYOUT_VEC 0   /* [n] fp32, zero padded                                  */
@@ -87,6 +91,9 @@ typedef struct {
   int vocab_size, hidden_size, intermediate_size, num_layers, max_positions;
   float layer_norm_eps;
   int quick_gelu;
+  /* StableDiffusionSafetyChecker (safety_checker/config.json "vision_config", "projection_dim"; the rows of
+     special_care_embeds / concept_embeds); the tower reuses hidden_size .. quick_gelu above */
+  int image_size, patch_size, projection_dim, n_special, n_concepts;
 } irx_model_config;
 
 typedef struct {
@@ -407,6 +414,46 @@ int irx_op_srvgg_conv(void* stream, const void* x, int batch, int H, int W, cons
 int irx_op_srvgg_tail(void* stream, const void* x, const uint8_t* in_u8, int batch, int H, int W, const float* in_lut,
                       const void* weight, const float* bias, uint8_t* out_u8, float* out_f);
 int irx_op_srvgg_prelu(void* stream, int dtype, const void* x, long rows, int C, const float* slope, void* out);
+
+/* ---- the Stable Diffusion safety checker (StableDiffusionImg2ImgPipeline.run_safety_checker, which ends the
+ * reference's img2img calls at src/inference.py:486, :566 and :664; switched off for inpainting, :444-451, :746-752) ----
+ * m is an IRX_MODEL_SAFETY model whose blob holds the checkpoint's `vision_model.vision_model.*` tower,
+ * `visual_projection.weight`, `special_care_embeds` / `concept_embeds` (rows already divided by max(|row|, 1e-12): the
+ * host normalises them once in fp64) and `special_care_embeds_weights` / `concept_embeds_weights` (the thresholds).
+ * crop_u8 [batch][S][S][3] in device memory, S = image_size: the decoded uint8 image after CLIPImageProcessor's resize
+ * (shortest edge to S, Pillow BICUBIC: irx_resample_u8 with the coefficient tables sliced to the crop window) and centre
+ * crop; in_lut = device float[256][3], the processor's rescale + normalise of byte v in channel c
+ * (safety_host.input_table).  scores [batch][n_special + n_concepts] = the fp32 cosines (special rows first, not
+ * rounded), flags int [batch] = has_nsfw_concept: adj = 0; every special row with rint(((cos - thr) + adj) * 1000) > 0
+ * sets adj = 0.01 for the rows after it; flagged if any concept row has rint(((cos - thr) + adj) * 1000) > 0 (numpy's
+ * round(x, 3) > 0 on float32, ties to even).  The tower's GEMMs are planned for the canonical batch and the head is one
+ * block per image with fixed-order sums: image i has the same scores at every batch size.  batch <= 64.
+ * ws: irx_safety_workspace_bytes(m, batch) bytes of device memory, 16-byte aligned.  A refused argument (null pointer,
+ * batch outside [1, 64], a model of another kind or without a bound blob, a short workspace) is a status and launches
+ * nothing.  Enqueues on `stream`: no allocation, no synchronisation.
+ * irx_safety_embed_u8: the fp32 image embeddings [batch][projection_dim] the head reads, without the head (tests).
+ * irx_safety_blank_u8: img[b] (uint8 [batch][H][W][3]) and, if not NULL, f01[b] (fp32, the same shape) become zeros
+ * for every b with flags[b] != 0: the black image run_safety_checker returns.  flags is device memory. */
+int irx_safety_workspace_bytes(const irx_model* m, int batch, size_t* bytes);
+int irx_safety_check_u8(irx_model* m, void* stream, const uint8_t* crop_u8, int batch, const float* in_lut,
+                        float* scores, int* flags, void* ws, size_t ws_bytes);
+int irx_safety_embed_u8(irx_model* m, void* stream, const uint8_t* crop_u8, int batch, const float* in_lut,
+                        float* embeds, void* ws, size_t ws_bytes);
+int irx_safety_blank_u8(void* stream, uint8_t* img, float* f01, int batch, int H, int W, const int* flags);
+/* the kernels of the checker on their own (tests).
+ * irx_op_safety_patches: crop_u8 [batch][S][S][3] -> out [batch * (S / patch)^2][kpad] of `dtype`, column
+ *   (c * patch + ky) * patch + kx = in_lut[byte][c] cast to dtype, columns [3 patch^2, kpad) zero.
+ * irx_op_safety_tokens: out[b][0] = cls + pos[0], out[b][1 + p] = patch_out[b][p] + pos[1 + p] (fp32 sum, one
+ *   rounding); patch_out [batch][P][D], pos [P + 1][D], out [batch][P + 1][D] of `dtype`; cls fp32 [D].
+ * irx_op_safety_head: embeds fp32 [batch][n]; special [n_special][n], concepts [n_concepts][n] (unit rows) and the
+ *   thresholds fp32 -> scores, flags as irx_safety_check_u8 writes them. */
+int irx_op_safety_patches(void* stream, int dtype, const uint8_t* crop_u8, int batch, int S, int patch, int kpad,
+                          const float* in_lut, void* out);
+int irx_op_safety_tokens(void* stream, int dtype, const void* patch_out, const float* cls, const void* pos, int batch,
+                         int P, int D, void* out);
+int irx_op_safety_head(void* stream, const float* embeds, int batch, int n, const float* special, int n_special,
+                       const float* concepts, int n_concepts, const float* thr_special, const float* thr_concepts,
+                       float* scores, int* flags);
 
 /* ---- multi-GPU: RCCL over xGMI (SURVEY.md §8b `irx_weights_bcast(handle, rcclComm)`, §8e) ----
    The reference has no multi-device path (src/inference.py:52-57 picks one device; it stands in for
