@@ -18,6 +18,7 @@ IRX_MODEL_LPIPS = 3       # LPIPS(alex), the reference's src/metrics.py:97-111
 IRX_MODEL_FID = 4         # InceptionV3 pooled features, the reference's src/metrics.py:70-80
 IRX_MODEL_SRVGG = 5       # Real-ESRGAN's SRVGGNetCompact, the reference's src/inference.py:335-336, :579-591
 IRX_MODEL_SAFETY = 6      # StableDiffusionSafetyChecker, run_safety_checker inside src/inference.py:486, :566, :664
+IRX_MODEL_RRDB = 7        # Real-ESRGAN's RRDBNet (RealESRGAN_x4plus.pth), the reference's src/inference.py:335-346, :579-591
 IRX_LAYOUT_VEC, IRX_LAYOUT_MAT, IRX_LAYOUT_CONV, IRX_LAYOUT_EMB = 0, 1, 2, 3
 IRX_LAYOUT_MAT_GEGLU64, IRX_LAYOUT_VEC_GEGLU64 = 4, 5
 IRX_LAYOUT_VEC_LN_U, IRX_LAYOUT_VEC_LN_V = 6, 7
@@ -155,6 +156,10 @@ _SIGS = {
     "irx_op_srvgg_conv": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "irx_op_srvgg_tail": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irx_op_srvgg_prelu": (i32, [vp, i32, vp, i64, i32, vp, vp]),
+    # Real-ESRGAN (RRDBNet, RealESRGAN_x4plus.pth): src/inference.py:335-346, :579-591
+    "irx_rrdb_workspace_bytes": (i32, [vp, i32, i32, i32, C.POINTER(sz)]),
+    "irx_rrdb_u8": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz]),
+    "irx_op_rrdb_conv": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, i32]),
     # SD safety checker: run_safety_checker inside the img2img calls, src/inference.py:486, :566, :664
     "irx_safety_workspace_bytes": (i32, [vp, i32, C.POINTER(sz)]),
     "irx_safety_check_u8": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, sz]),

@@ -38,6 +38,8 @@ PER_FILE = {"elementwise.hip": ["-ffp-contract=off"],
             "fid.hip": ["-ffp-contract=off"],
             # the SRVGG epilogues and tail as srvgg_host.py writes them: slope * v, + bias, + x, * 255 each on its own
             "srvgg.hip": ["-ffp-contract=off"],
+            # the RRDB epilogues as rrdb_host.py writes them: 0.2f * v, + bias, + x each rounded on its own
+            "rrdb.hip": ["-ffp-contract=off"],
             # the safety checker's decision as numpy writes it: cos - thr, + adj, * 1000 each rounded on its own
             "safety.hip": ["-ffp-contract=off"],
             # Pillow's coefficient doubles: libm's sin, IEEE divisions, no FMA (csrc/resample_coeffs.cpp)

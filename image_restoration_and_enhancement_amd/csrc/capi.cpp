@@ -130,6 +130,9 @@ static const struct { const char* name; int* i; bool* b; } kOpts[] = {
     {"nlm2_strip", &g_nlm2_strip, nullptr},
     {"srvgg_fused", &g_srvgg_fused, nullptr},
     {"srvgg_blocks", &g_srvgg_blocks, nullptr},
+    {"rrdb_fused", &g_rrdb_fused, nullptr},
+    {"rrdb_blocks", &g_rrdb_blocks, nullptr},
+    {"rrdb_resident", &g_rrdb_resident, nullptr},
 };
 static OptRef opt_ref(const std::string& n) {
   for (const auto& o : kOpts)
@@ -235,6 +238,7 @@ int irx_model_create(int kind, const irx_model_config* cfg, int dtype, irx_model
     else if (kind == IRX_MODEL_FID) h->m.reset(new InceptionFid(*cfg, dtype));
     else if (kind == IRX_MODEL_SRVGG) h->m.reset(new Srvgg(*cfg, dtype));
     else if (kind == IRX_MODEL_SAFETY) h->m.reset(new SafetyChecker(*cfg, dtype));
+    else if (kind == IRX_MODEL_RRDB) h->m.reset(new Rrdb(*cfg, dtype));
     else throw Error("unknown model kind");
   } catch (...) {
     delete h;
@@ -828,6 +832,35 @@ int irx_op_srvgg_tail(void* s, const void* x, const uint8_t* in_u8, int B, int H
 int irx_op_srvgg_prelu(void* s, int dtype, const void* x, long rows, int C, const float* slope, void* out) {
   IRX_API_BEGIN
   srvgg_prelu(dtype, x, rows, C, slope, out, S(s));
+  IRX_API_END
+}
+// ------------------------------------------------------------------ Real-ESRGAN RRDBNet (rrdb_model.cpp, rrdb.hip;
+// the network of RealESRGAN_x4plus.pth, src/inference.py:335-346; RestorationPipeline._sr_realesrgan, :579-591)
+int irx_rrdb_workspace_bytes(const irx_model* m, int B, int H, int W, size_t* bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(bytes, "null argument");
+  *bytes = const_cast<Rrdb*>(as<Rrdb>(m, IRX_MODEL_RRDB))->workspace_bytes(B, H, W);
+  IRX_API_END
+}
+int irx_rrdb_u8(irx_model* m, void* s, const uint8_t* in_u8, int B, int H, int W, const float* in_lut, uint8_t* out_u8,
+                float* out_f, void* ws, size_t ws_bytes) {
+  IRX_API_BEGIN
+  IRX_CHECK(in_u8 && in_lut && out_u8 && ws, "null image, table, output or workspace pointer");
+  IRX_CHECK(B > 0 && H >= 1 && W >= 1, "RRDB: batch, H and W must be positive");
+  as<Rrdb>(m, IRX_MODEL_RRDB)->enhance(S(s), in_u8, B, H, W, in_lut, out_u8, out_f, (char*)ws, ws_bytes);
+  IRX_API_END
+}
+int irx_op_rrdb_conv(void* s, const void* x, int ldx, int cin, int B, int H, int W, const void* w, const float* bias,
+                     int cout, int lrelu, const void* res1, int ldr1, int res1_scaled, const void* res2, int ldr2,
+                     void* out, int ldo) {
+  IRX_API_BEGIN
+  RrdbConv a;
+  a.x = x; a.ldx = ldx; a.cin = cin;
+  a.w = w; a.bias = bias; a.cout = cout; a.lrelu = lrelu;
+  a.r1 = res1; a.ldr1 = ldr1; a.r1_scaled = res1_scaled; a.r2 = res2; a.ldr2 = ldr2;
+  a.y = out; a.ldy = ldo;
+  a.B = B; a.H = H; a.W = W;
+  rrdb_conv(a, S(s));
   IRX_API_END
 }
 // ------------------------------------------------------------------ single ops

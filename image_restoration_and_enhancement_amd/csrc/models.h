@@ -348,4 +348,31 @@ class Srvgg : public Model {
   int cin0_ = 4;
 };
 
+// Real-ESRGAN's RRDBNet(3, 3, num_feat=64, num_block, num_grow_ch=32, scale=4) (rrdb_host.py; the network of
+// RealESRGAN_x4plus.pth, the file the reference names at src/inference.py:326-350; enhance, :579-591): uint8 RGB in,
+// uint8 RGB x4 out.  fp16 is the product (the slab conv kernel of rrdb.hip, or conv2d + glue kernels with rrdb_fused =
+// 0), fp32 the parity engine on gemm()'s exact-f32 path; bf16 is refused.  The config gives num_block (num_layers),
+// num_feat (hidden_size) and num_grow_ch (intermediate_size).
+class Rrdb : public Model {
+ public:
+  Rrdb(const irx_model_config& cfg, int dtype);
+  static constexpr int kFeat = 64, kGrow = 32, kWide = kFeat + 4 * kGrow, kLastPad = 8;
+  size_t workspace_bytes(int B, int H, int W);
+  void enhance(hipStream_t s, const uint8_t* img, int B, int H, int W, const float* lut, uint8_t* out_u8,
+               float* out_f, char* ws, size_t cap);
+
+ private:
+  struct Cv { P w, b; };
+  struct Rdb { Cv c[5]; };
+  void run(Ctx& c, const uint8_t* img, int B, int H, int W, const float* lut, uint8_t* out_u8, float* out_f);
+  void run_fused(Ctx& c, const uint8_t* img, int B, int H, int W, const float* lut, uint8_t* out_u8, float* out_f);
+  // the conv2d graph's form of one rrdb_conv call: gather (unless x is dense), conv2d to an fp32 sum, epilogue
+  void conv_glue(Ctx& c, const void* x, int ldx, int cin, int B, int Hs, int Ws, int up, const Cv& cv, int cout,
+                 int lrelu, const void* r1, int ldr1, int r1_scaled, const void* r2, int ldr2, void* y, int ldy);
+  Cv make(const std::string& name, int co, int ci);
+  int nb_ = 0, cin0_ = 4;
+  Cv first_, body_, up1_, up2_, hr_, last_;
+  std::vector<Rdb> rdb_;   // 3 per RRDB
+};
+
 }  // namespace irx

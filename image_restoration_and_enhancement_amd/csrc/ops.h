@@ -442,4 +442,41 @@ void safety_head(const float* emb, int B, int n, const float* special, int ns, c
 // img[b][0, n) = 0 (and f01[b][0, n), if not null) for every b with flags[b] != 0
 void safety_blank(uint8_t* img, float* f01, int B, long n, const int* flags, hipStream_t s);
 
+// ------------------------------------------------------------ Real-ESRGAN RRDBNet (rrdb.hip; Rrdb, models.h)
+extern int g_rrdb_fused;    // 1: the fp16 engine runs the slab conv kernel of rrdb.hip (0: conv2d + glue kernels, A/B)
+extern int g_rrdb_blocks;   // persistent blocks of the slab conv kernel's grid (0: one per CU)
+// a conv whose whole weight panel fits the LDS next to two halo slabs keeps it there: 1 from 16 tiles per block, 2
+// always, 0 never
+extern int g_rrdb_resident;
+// One 3x3 / pad 1 conv of the fp16 engine (rrdb_conv_kernel).  Channels [0, cin) of x are read, pixels ldx elements
+// apart; with `up` x is the [B][H / 2][W / 2] tensor and the conv sees its nearest x2 (H, W even).  v = r16(acc +
+// r16(bias)); lrelu: v > 0 ? v : r16(0.2f v); r1: v = r16((r1_scaled ? r16(0.2f v) : v) + r1); r2: v = r16(r16(0.2f v)
+// + r2).  y points at the first channel of the destination slice (y == r2 allowed).  With out_u8 the conv is
+// conv_last: cout = 3, the value goes to out_u8 [B][H][W][3] (clamp, * 255, rint) and, unclamped, to out_f if not null.
+struct RrdbConv {
+  const void* x = nullptr; int ldx = 0, cin = 0, up = 0;
+  const void* w = nullptr;          // fp16 [cout][3][3][cin]
+  const float* bias = nullptr;      // fp32 [cout]
+  int cout = 0, lrelu = 0;          // 32 or 64 (3 with out_u8)
+  const void* r1 = nullptr; int ldr1 = 0, r1_scaled = 0;
+  const void* r2 = nullptr; int ldr2 = 0;
+  void* y = nullptr; int ldy = 0;
+  uint8_t* out_u8 = nullptr; float* out_f = nullptr;
+  int B = 0, H = 0, W = 0;          // the output's size
+};
+void rrdb_conv(const RrdbConv& a, hipStream_t s);
+// conv_first of the fp16 engine: uint8 [B][H][W][3] -> lut -> fp16 -> conv 3 -> 64 (w's Cin padded to cp) + bias, no
+// activation, written to y (pixels ldy apart) and to y2 (ldy2) if not null
+void rrdb_head(const uint8_t* img, int B, int H, int W, const float* lut, const void* w, int cp, const float* bias,
+               void* y, int ldy, void* y2, int ldy2, hipStream_t s);
+// the glue of the conv2d graph (dtype F32 or F16; T below): channels [0, C) of x (pixels ldx apart) -> y [rows][C]
+void rrdb_gather(int dtype, const void* x, int ldx, long rows, int C, void* y, hipStream_t s);
+// the epilogue of rrdb_conv on a stored fp32 conv sum acc [rows][C] (no bias): rounding to T where rrdb_conv rounds to
+// fp16 (T = float: no rounding, bias read unrounded); y, r1, r2 of T with their strides
+void rrdb_epilogue(int dtype, const float* acc, long rows, int C, const float* bias, int lrelu, const void* r1,
+                   int ldr1, int r1_scaled, const void* r2, int ldr2, void* y, int ldy, hipStream_t s);
+// conv_last's end on acc fp32 [rows][ldacc] (no bias): + bias, rounded to T -> out_u8 [rows][3], out_f or null
+void rrdb_output(int dtype, const float* acc, int ldacc, long rows, const float* bias, uint8_t* out_u8, float* out_f,
+                 hipStream_t s);
+
 }  // namespace irx

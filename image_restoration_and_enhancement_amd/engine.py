@@ -36,6 +36,10 @@ def model_config(kind: int, cfg) -> L.ModelConfig:
     c = L.ModelConfig()
     if kind in (L.IRX_MODEL_LPIPS, L.IRX_MODEL_FID, L.IRX_MODEL_SRVGG):       # fixed architecture: the native model does not read the config
         return c
+    if kind == L.IRX_MODEL_RRDB:      # include/irx.h: num_block, num_feat, num_grow_ch in three existing fields
+        if cfg is not None:
+            c.num_layers, c.hidden_size, c.intermediate_size = cfg.num_block, cfg.num_feat, cfg.num_grow_ch
+        return c
     if kind == L.IRX_MODEL_UNET:
         assert isinstance(cfg, UNetConfig)
         c.in_channels, c.out_channels = cfg.in_channels, cfg.out_channels

@@ -35,6 +35,8 @@ Differences that follow from the engine (documented in INTEGRATION.md):
   reference constructs (src/inference.py:335-336) from a weight file the user names: `config["sr"]
   ["realesrgan_weights"]` or the environment variable IRX_REALESRGAN_WEIGHTS (a file, or a directory holding one
   `*.pth` / `*.safetensors`).  Nothing is downloaded; with nothing configured the backend behaves as before.
+  `config["sr"]["realesrgan_arch"]` (or IRX_REALESRGAN_ARCH) picks the network: "srvgg" (default), "rrdbnet" for
+  `RealESRGAN_x4plus.pth`, the file the reference names (src/inference.py:326-350), or "auto" by the file's keys.
 """
 from __future__ import annotations
 
@@ -93,29 +95,58 @@ class NativeSDModel:
 
 class RealESRGANModel:
     """What `models["sr"]` holds when Real-ESRGAN serves super-resolution: an object with an `enhance` method, which
-    is what the reference dispatches on (`hasattr(model, 'enhance')`, src/inference.py:538).  On a ROCm device it wraps
-    `srvgg_gpu.RealESRGANCompact` in fp16 (the reference's `half=self.device == "cuda"`), on the CPU
-    `srvgg_host.enhance` in fp32."""
+    is what the reference dispatches on (`hasattr(model, 'enhance')`, src/inference.py:538).  `arch` is the network the
+    weights belong to: "srvgg" (SRVGGNetCompact, the one the reference constructs) or "rrdbnet" (RRDBNet, the one
+    `RealESRGAN_x4plus.pth` holds).  On a ROCm device it wraps `srvgg_gpu.RealESRGANCompact` / `rrdb_gpu.
+    RealESRGANx4plus` in fp16 (the reference's `half=self.device == "cuda"`), on the CPU `srvgg_host.enhance` /
+    `rrdb_host.enhance` in fp32."""
 
-    def __init__(self, weights, device: str, source: str):
+    def __init__(self, weights, device: str, source: str, arch: str = "srvgg"):
+        if arch not in ("srvgg", "rrdbnet"):
+            raise ValueError(f"RealESRGANModel: arch 'srvgg' or 'rrdbnet', not {arch!r}")
         self.device = device
         self.source = source
+        self.arch = arch
         self.net = None
         self.weights = weights
         if str(device).startswith("cuda"):
-            from . import srvgg_gpu
-            self.net = srvgg_gpu.RealESRGANCompact(weights, device, "fp16")
+            if arch == "rrdbnet":
+                from . import rrdb_gpu
+                self.net = rrdb_gpu.RealESRGANx4plus(weights, device, "fp16")
+            else:
+                from . import srvgg_gpu
+                self.net = srvgg_gpu.RealESRGANCompact(weights, device, "fp16")
 
     def enhance(self, images: np.ndarray) -> np.ndarray:
         """uint8 RGB [H, W, 3] or [B, H, W, 3] -> the uint8 x4 result (numpy)."""
         if self.net is not None:
             return self.net.enhance(np.ascontiguousarray(images)).cpu().numpy()
-        from . import srvgg_host
-        out = srvgg_host.enhance(np.ascontiguousarray(images), self.weights, torch.float32, half=False)
+        if self.arch == "rrdbnet":
+            from . import rrdb_host as host
+        else:
+            from . import srvgg_host as host
+        out = host.enhance(np.ascontiguousarray(images), self.weights, torch.float32, half=False)
         return out if isinstance(out, np.ndarray) else out.numpy()
 
     def __repr__(self):
-        return f"RealESRGANModel({self.source})"
+        tail = "" if self.arch == "srvgg" else f", {self.arch}"
+        return f"RealESRGANModel({self.source}{tail})"
+
+
+def _load_realesrgan(src, arch: str):
+    """(weights, arch) of the Real-ESRGAN file `src` for `realesrgan_arch` = "srvgg" (the default: the compact net
+    the reference constructs; an RRDBNet file is refused with its keys), "rrdbnet", or "auto" (RRDBNet if the key set
+    is one, else the compact net, whose check names the keys of a file that fits neither)."""
+    from . import srvgg_host
+    if arch == "srvgg":
+        return srvgg_host.load_weights(src), "srvgg"
+    if arch not in ("rrdbnet", "auto"):
+        raise ValueError(f"realesrgan_arch: 'srvgg', 'rrdbnet' or 'auto', not {arch!r}")
+    from . import rrdb_host
+    sd = rrdb_host.read_file(src)
+    if arch == "rrdbnet" or rrdb_host.looks_like_rrdb(sd):
+        return rrdb_host.check_weights(sd), "rrdbnet"
+    return srvgg_host.check_weights(sd), "srvgg"
 
 
 def _resolve_pretrained(repo_id: str) -> Path:
@@ -300,8 +331,10 @@ class RestorationPipeline:
             src = self.config["sr"].get("realesrgan_weights") or os.environ.get("IRX_REALESRGAN_WEIGHTS")
             if src:
                 try:
-                    from . import srvgg_host
-                    self.models["sr"] = RealESRGANModel(srvgg_host.load_weights(src), self.device, str(src))
+                    arch = (self.config["sr"].get("realesrgan_arch") or os.environ.get("IRX_REALESRGAN_ARCH")
+                            or "srvgg")
+                    weights, arch = _load_realesrgan(src, str(arch).lower())
+                    self.models["sr"] = RealESRGANModel(weights, self.device, str(src), arch)
                     logger.info(f"Super-resolution model ready (Real-ESRGAN, {src})")
                     return
                 except IrxError:

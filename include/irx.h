@@ -38,6 +38,12 @@ extern "C" {
  * :566, :664): the CLIP vision tower in the model dtype, the cosine head in fp32.  Reads hidden_size, intermediate_size,
  * num_layers, heads, layer_norm_eps, quick_gelu and the five safety fields at the end of irx_model_config */
 #define IRX_MODEL_SAFETY 6
+/* Real-ESRGAN's RRDBNet(3, 3, num_feat=64, num_block, num_grow_ch=32, scale=4), the network RealESRGAN_x4plus.pth
+ * belongs to (the file src/inference.py:326-350 names): IRX_F16 (the product) or IRX_F32 (parity); IRX_BF16 is refused
+ * at creation.  Reads three existing fields of irx_model_config, so the struct does not grow: num_layers = num_block
+ * (1..64), hidden_size = num_feat and intermediate_size = num_grow_ch (the kernels are built for 64 and 32; any other
+ * value is refused at creation) */
+#define IRX_MODEL_RRDB 7
 
 /* weight layouts of manifest entries (how the host packs diffusers tensors into the blob) */
 #define IRX_LAYOUT_VEC 0   /* [n] fp32, zero padded                                  */
@@ -454,6 +460,41 @@ int irx_op_safety_tokens(void* stream, int dtype, const void* patch_out, const f
 int irx_op_safety_head(void* stream, const float* embeds, int batch, int n, const float* special, int n_special,
                        const float* concepts, int n_concepts, const float* thr_special, const float* thr_concepts,
                        float* scores, int* flags);
+
+/* ---- Real-ESRGAN, the RRDBNet of RealESRGAN_x4plus.pth (the RealESRGANer the reference builds at
+ * src/inference.py:335-346 around the file it names, and model.enhance in _sr_realesrgan, :579-591, at outscale 4,
+ * tile 0, pre_pad 0) ----
+ * m is an IRX_MODEL_RRDB model whose blob holds `conv_first`, `body.{0..num_block-1}.rdb{1,2,3}.conv{1..5}`,
+ * `conv_body`, `conv_up1`, `conv_up2`, `conv_hr`, `conv_last` (.weight / .bias), the keys of RealESRGAN_x4plus.pth.
+ * in_u8 [batch][H][W][3] RGB in device memory, H, W >= 1; in_lut = device float[256], float32(v) / 255
+ * (srvgg_host.input_table); out_u8 [batch][4H][4W][3] = round_half_even(clamp(net(x), 0, 1) * 255); out_f (NULL: not
+ * wanted) fp32 of the same shape = net(x) before the clamp.  net: feat = conv_first(x); 23 x RRDB (three dense blocks
+ * x5 * 0.2 + x, then * 0.2 + the RRDB's input); feat += conv_body(.); lrelu(conv_up1(nearest x2)); lrelu(conv_up2(
+ * nearest x2)); conv_last(lrelu(conv_hr(.))); LeakyReLU slope 0.2.  An IRX_F16 model accumulates in fp32 and rounds to
+ * fp16 after each conv + bias (bias read as fp16), each LeakyReLU (v > 0 ? v : fp16(0.2f * v)) and each step of
+ * fp16(fp16(0.2f * t) + x): PyTorch's eager fp16 rounding points (the kernels of rrdb.hip; option rrdb_fused = 0: the
+ * same graph and rounding points on the general conv kernels).  An IRX_F32 model runs every conv in exact fp32.  The
+ * same bits on every run and at every batch position.
+ * ws: irx_rrdb_workspace_bytes(m, batch, H, W) bytes of device memory, 16-byte aligned (it depends on rrdb_fused).
+ * The fused kernels index with 64-bit offsets; the general conv kernels count elements in an int, so on that path
+ * batch * 4H * 4W * 64 > INT_MAX is refused.  A refused argument (null pointer, batch <= 0, H or W < 1, a size limit, a
+ * model of another kind or without a bound blob, a short workspace) is a status and launches nothing.  Enqueues on
+ * `stream`: no allocation, no synchronisation. */
+int irx_rrdb_workspace_bytes(const irx_model* m, int batch, int H, int W, size_t* bytes);
+int irx_rrdb_u8(irx_model* m, void* stream, const uint8_t* in_u8, int batch, int H, int W, const float* in_lut,
+                uint8_t* out_u8, float* out_f, void* ws, size_t ws_bytes);
+/* the body kernel of that network on its own (tests): one 3x3 / pad 1 conv of the dense block, as the fp16 engine
+ * calls it for RRDBNet's forward (basicsr rrdbnet_arch.py; what model.enhance runs at src/inference.py:579-591).
+ * x: fp16 NHWC [batch][H][W] pixels ldx elements apart, channels [0, cin) read, cin a multiple of 32 in [32, 192];
+ * weight fp16 [cout][3][3][cin], cout 32 or 64; bias fp32 [cout], rounded to fp16 when read.
+ * v = fp16(conv + bias); lrelu != 0: v = v > 0 ? v : fp16(0.2f * v); res1 != NULL: v = fp16((res1_scaled ?
+ * fp16(0.2f * v) : v) + res1[pixel * ldr1 + c]); res2 != NULL: v = fp16(fp16(0.2f * v) + res2[pixel * ldr2 + c]);
+ * out[pixel * ldo + c] = v for c in [0, cout): `out` points at the first channel of the slice and nothing else is
+ * written.  out may equal res2 (the end of an RRDB) but must not overlap the channels of x that are read.
+ * ldx, ldo % 8 == 0, ldr1, ldr2 % 4 == 0; x and weight 16-byte, out, res1 and res2 8-byte aligned. */
+int irx_op_rrdb_conv(void* stream, const void* x, int ldx, int cin, int batch, int H, int W, const void* weight,
+                     const float* bias, int cout, int lrelu, const void* res1, int ldr1, int res1_scaled,
+                     const void* res2, int ldr2, void* out, int ldo);
 
 /* ---- multi-GPU: RCCL over xGMI (SURVEY.md §8b `irx_weights_bcast(handle, rcclComm)`, §8e) ----
    The reference has no multi-device path (src/inference.py:52-57 picks one device; it stands in for
