@@ -123,6 +123,11 @@ _SIGS = {
     "irx_degrade_motion_blur": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "irx_degrade_jpeg_ws_bytes": (i64, [i32, i32, i32]),
     "irx_degrade_jpeg": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp]),
+    # PIL.Image.save on a .jpg name (scripts/generate_predictions.py:83-84)
+    "irx_jpeg_encode_ws_bytes": (i64, [i32, i32, i32]),
+    "irx_jpeg_encode_bound": (i64, [i32, i32]),
+    "irx_jpeg_encode": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp, i64, vp]),
+    "irx_jpeg_header": (i32, [i32, i32, vp, vp, i32]),
     "irx_nlm_weights": (i32, [f32, i32, i32, i32, C.POINTER(i32), i32, C.POINTER(i32)]),
     "irx_nlmeans_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32]),
     "irx_bilateral_tables": (i32, [i32, C.c_double, C.c_double, i32, vp, vp, vp, i32, C.POINTER(i32),
@@ -250,6 +255,10 @@ def load(path: Path | str | None = None, force: bool = False):
 def call(name: str, *args):
     lib = load()
     rc = getattr(lib, name)(*args)
+    if name == "irx_jpeg_header":                   # returns a length; negative: refused
+        if rc < 0:
+            raise IrxError(f"{name}: {lib.irx_last_error().decode(errors='replace')}")
+        return rc
     if _SIGS[name][0] is i32 and name not in ("irx_version", "irx_rccl_available") and rc != 0:
         raise IrxError(f"{name}: {lib.irx_last_error().decode(errors='replace')}")
     return rc

@@ -508,6 +508,24 @@ int irx_degrade_jpeg(void* s, const uint8_t* img, int batch, int H, int W, const
   IRX_API_END
 }
 
+// ------------------------------------------------------------------ baseline JPEG encoder (irx_jpeg_header: jpeg_header.cpp)
+static bool jpeg_dims_ok(int batch, int H, int W) {
+  return batch >= 0 && H >= 8 && W >= 8 && H <= 65535 && W <= 65535;
+}
+long irx_jpeg_encode_ws_bytes(int batch, int H, int W) {
+  return jpeg_dims_ok(batch, H, W) ? jpeg_encode_ws_bytes(batch, H, W) : 0;
+}
+long irx_jpeg_encode_bound(int H, int W) { return jpeg_dims_ok(0, H, W) ? jpeg_encode_bound(H, W) : 0; }
+int irx_jpeg_encode(void* s, const uint8_t* img, int batch, int H, int W, const int* qtables, int rgb, void* ws,
+                    uint8_t* out, long out_stride, int* lens) {
+  IRX_API_BEGIN
+  IRX_CHECK(H >= 8 && W >= 8 && H <= 65535 && W <= 65535, "JPEG encode: 8 <= H, W <= 65535");
+  IRX_CHECK(img && qtables && out && lens && batch >= 0 && (ws || batch == 0), "JPEG encode: bad arguments");
+  IRX_CHECK(out_stride >= jpeg_encode_bound(H, W), "JPEG encode: out_stride below irx_jpeg_encode_bound(H, W)");
+  if (batch) jpeg_encode(img, batch, H, W, qtables, rgb, ws, out, out_stride, lens, S(s));
+  IRX_API_END
+}
+
 // ------------------------------------------------------------------ fast non-local means
 static int nlm_shift(int tmpl) {
   int s = 0;

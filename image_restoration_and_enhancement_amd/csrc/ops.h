@@ -353,6 +353,12 @@ void degrade_motion_blur(const uint8_t* img, int B, int H, int W, int C, const i
 long degrade_jpeg_ws_bytes(int B, int H, int W);
 void degrade_jpeg(const uint8_t* img, int B, int H, int W, const int* qt_dev, int rgb, void* ws, uint8_t* out,
                   hipStream_t s);
+// baseline JPEG encoder (jpeg_encode.hip): the scan of every image to out + b * out_stride, its length to lens[b]
+// (device); out_stride >= jpeg_encode_bound; ws of jpeg_encode_ws_bytes, 16-byte aligned, contents arbitrary
+long jpeg_encode_bound(int H, int W);
+long jpeg_encode_ws_bytes(int B, int H, int W);
+void jpeg_encode(const uint8_t* img, int B, int H, int W, const int* qt_dev, int rgb, void* ws, uint8_t* out,
+                 long out_stride, int* lens, hipStream_t s);
 
 
 // ------------------------------------------------------------ fast non-local means (nlmeans.hip)

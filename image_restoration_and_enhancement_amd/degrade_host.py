@@ -147,14 +147,20 @@ def _idct_pass(c, n: int):
     return np.stack([_descale(o, n) for o in out], -1)
 
 
-def _codec_plane(plane: np.ndarray, q: np.ndarray) -> np.ndarray:
-    """plane int64 [8a][8b] samples 0..255 -> reconstructed samples after DCT, quantise, dequantise, IDCT."""
+def _quantise_plane(plane: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """plane int64 [8a][8b] samples 0..255 -> quantised DCT coefficients [a][b][row][col] (jcdctmgr's division)."""
     Hp, Wp = plane.shape
     blk = (plane - 128).reshape(Hp // 8, 8, Wp // 8, 8).transpose(0, 2, 1, 3)       # [by][bx][row][col]
     c = _fdct_pass(blk, True)                                                         # rows
     c = _fdct_pass(c.swapaxes(-1, -2), False).swapaxes(-1, -2)                        # columns
     q8 = q.astype(np.int64).reshape(8, 8) * 8
-    c = np.sign(c) * ((np.abs(c) + (q8 >> 1)) // q8)
+    return np.sign(c) * ((np.abs(c) + (q8 >> 1)) // q8)
+
+
+def _codec_plane(plane: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """plane int64 [8a][8b] samples 0..255 -> reconstructed samples after DCT, quantise, dequantise, IDCT."""
+    Hp, Wp = plane.shape
+    c = _quantise_plane(plane, q)
     c = c * q.astype(np.int64).reshape(8, 8)
     c = _idct_pass(c.swapaxes(-1, -2), _CONST_BITS - _PASS1_BITS).swapaxes(-1, -2)    # columns
     c = _idct_pass(c, _CONST_BITS + _PASS1_BITS + 3)                                  # rows
@@ -178,6 +184,27 @@ def _upsample_h2v2_fancy(c: np.ndarray, H: int, W: int) -> np.ndarray:
     return (3 * s[:, cx] + s[:, nx] + bias) >> 4
 
 
+def _to_ycbcr(img: np.ndarray, rgb: bool):
+    """uint8 [H][W][3] -> int64 Y, Cb, Cr planes (jccolor.c, 16-bit fixed point)."""
+    x = img.astype(np.int64)
+    R, G, B = (x[..., 0], x[..., 1], x[..., 2]) if rgb else (x[..., 2], x[..., 1], x[..., 0])
+    Y = (_fix(.299) * R + _fix(.587) * G + _fix(.114) * B + 32768) >> 16
+    Cb = (-_fix(.16874) * R - _fix(.33126) * G + _fix(.5) * B + (128 << 16) + 32767) >> 16
+    Cr = (_fix(.5) * R - _fix(.41869) * G - _fix(.08131) * B + (128 << 16) + 32767) >> 16
+    return Y, Cb, Cr
+
+
+def _downsample_h2v2(p: np.ndarray) -> np.ndarray:
+    """A full-resolution chroma plane [H][W] -> its 4:2:0 plane padded to whole MCUs [H16 / 2][W16 / 2]: columns
+    replicated to W16 before the 2x2 average (bias 1, 2 alternating), rows replicated after it."""
+    H, W = p.shape
+    H16, W16 = -(-H // 16) * 16, -(-W // 16) * 16
+    p = _pad_edge(p, 2 * ((H + 1) // 2), W16)
+    bias = np.where(np.arange(W16 // 2) % 2 == 0, 1, 2)
+    d = (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + bias) >> 2
+    return _pad_edge(d, H16 // 2, W16 // 2)
+
+
 def jpeg_roundtrip_ref(img: np.ndarray, quality: int, rgb: bool = False) -> np.ndarray:
     """uint8 [H][W][3] (BGR, or RGB with rgb=True) -> the decoded pixels of its quality-`quality` 4:2:0
     baseline JPEG, in the same channel order."""
@@ -186,20 +213,13 @@ def jpeg_roundtrip_ref(img: np.ndarray, quality: int, rgb: bool = False) -> np.n
         raise ValueError("expected [H][W][3]")
     H, W = img.shape[:2]
     qt = jpeg_quant_tables(quality)
-    x = img.astype(np.int64)
-    R, G, B = (x[..., 0], x[..., 1], x[..., 2]) if rgb else (x[..., 2], x[..., 1], x[..., 0])
-    Y = (_fix(.299) * R + _fix(.587) * G + _fix(.114) * B + 32768) >> 16
-    Cb = (-_fix(.16874) * R - _fix(.33126) * G + _fix(.5) * B + (128 << 16) + 32767) >> 16
-    Cr = (_fix(.5) * R - _fix(.41869) * G - _fix(.08131) * B + (128 << 16) + 32767) >> 16
+    Y, Cb, Cr = _to_ycbcr(img, rgb)
     H16, W16 = -(-H // 16) * 16, -(-W // 16) * 16
     CH, CW = (H + 1) // 2, (W + 1) // 2
     Yr = _codec_plane(_pad_edge(Y, H16, W16), qt[0])[:H, :W]
 
     def chroma(p):
-        p = _pad_edge(p, 2 * CH, W16)
-        bias = np.where(np.arange(W16 // 2) % 2 == 0, 1, 2)
-        d = (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + bias) >> 2
-        r = _codec_plane(_pad_edge(d, H16 // 2, W16 // 2), qt[1])
+        r = _codec_plane(_downsample_h2v2(p), qt[1])
         return _upsample_h2v2_fancy(r[:CH, :CW], H, W) - 128
 
     cb, cr = chroma(Cb), chroma(Cr)

@@ -375,8 +375,9 @@ class RestorationPipeline:
 
     # ------------------------------------------------------------------------------------ engine calls
     def _img2img(self, model: NativeSDModel, images: Sequence[Image.Image], prompt: Optional[str],
-                 strength: float, steps: int, guidance: float) -> List[Image.Image]:
-        """Same-size RGB PIL images -> restored PIL images (size rounded down to a multiple of 8)."""
+                 strength: float, steps: int, guidance: float, jpeg_quality: Optional[int] = None):
+        """Same-size RGB PIL images -> restored PIL images (size rounded down to a multiple of 8); with
+        `jpeg_quality`, the JPEG file of each instead, encoded on the device (jpeg_gpu.encode)."""
         if prompt is None:
             raise ValueError("Provide either `prompt` or `prompt_embeds`.")
         # each image's bytes are uploaded as they are and snapped to a multiple of 8 on the device (same bytes as
@@ -385,7 +386,7 @@ class RestorationPipeline:
         if dev.shape[1] < 8 or dev.shape[2] < 8:
             raise ValueError(f"image too small for the VAE: {images[0].size}")
         res = model.engine.img2img(dev, prompt, strength, steps, guidance, seed=self.seed)
-        out = [Image.fromarray(a) for a in res.images_u8.cpu().numpy()]
+        out = self._from_device(res.images_u8, jpeg_quality)
         # the flags come back with the image (flagged rows are already black on the device)
         nsfw = getattr(res, "nsfw", None)
         self.last_nsfw = [None] * len(out) if nsfw is None else [bool(f) for f in nsfw.cpu().numpy()]
@@ -395,13 +396,34 @@ class RestorationPipeline:
         return out
 
     def _inpaint_native(self, model: NativeSDModel, images: Sequence[Image.Image], masks: Sequence[Image.Image],
-                        prompt: str, strength: float, steps: int, guidance: float) -> List[Image.Image]:
+                        prompt: str, strength: float, steps: int, guidance: float,
+                        jpeg_quality: Optional[int] = None):
         S = INPAINT_SIZE
         # images (of any size) and masks are squashed to 512x512 on the device; the mask is binarised there
         res = model.engine.inpaint(ip.images_to_device(images, self.device, S, S),
                                    ip.masks_to_device(masks, self.device, S, S), prompt, strength, steps,
                                    guidance, seed=self.seed)
-        return [Image.fromarray(a) for a in res.images_u8.cpu().numpy()]
+        return self._from_device(res.images_u8, jpeg_quality)
+
+    @staticmethod
+    def _from_device(images_u8, jpeg_quality: Optional[int]):
+        """A uint8 [B][H][W][3] device batch -> PIL images, or (jpeg_quality given) the bytes `Image.save` would
+        write for each as a JPEG of that quality, without moving the pixels to the host."""
+        if jpeg_quality is None:
+            return [Image.fromarray(a) for a in images_u8.cpu().numpy()]
+        from . import jpeg_gpu
+        return jpeg_gpu.encode(images_u8, jpeg_quality)
+
+    @staticmethod
+    def _jpeg_bytes(result, quality: int) -> bytes:
+        """A result of restore_batch(output="jpeg") that is still a PIL image (passed through, or from a path that
+        does not end on the device): the file PIL itself writes for it."""
+        if isinstance(result, bytes):
+            return result
+        import io
+        buf = io.BytesIO()
+        result.save(buf, "JPEG", quality=quality)
+        return buf.getvalue()
 
     # ------------------------------------------------------------------------------------ denoise
     def denoise(self, image: Image.Image, strength: float = 0.5, **kwargs) -> Image.Image:
@@ -650,7 +672,7 @@ class RestorationPipeline:
     # ------------------------------------------------------------------------------------ batched API
     def restore_batch(self, task: str, images: Sequence[Image.Image], masks: Optional[Sequence] = None,
                       prompt: Optional[str] = None, strength: Optional[float] = None,
-                      max_batch: int = 8) -> List[Image.Image]:
+                      max_batch: int = 8, output: str = "pil", jpeg_quality: int = 75):
         """Batched form of the single-image entry points (new; the reference loops one image per call).
         Images of equal processed size run as one engine batch of up to `max_batch`; each image gets the
         result the single-image call returns (per-call reseeded noise).  The result does not depend on the
@@ -658,7 +680,15 @@ class RestorationPipeline:
         16-image batch of the per-image shape and GroupNorm partials are per image, so batch 8
         == 3 + 5 bit for bit on every engine (tests/test_batch_invariance_gpu.py).  Falls back to the
         single-image entry point per image (with the caller's prompt) whenever that one would not take the
-        diffusion path."""
+        diffusion path.
+
+        output="jpeg": a List[bytes] instead, one per input in input order: the file saving the "pil" result as a
+        JPEG of `jpeg_quality` would give (PIL.Image.save on a .jpg name, scripts/generate_predictions.py:83-84),
+        encoded on the device for the diffusion path (a safety-flagged image gives the file of the black image)."""
+        if output not in ("pil", "jpeg"):
+            raise ValueError(f"output must be 'pil' or 'jpeg', not {output!r}")
+        jq = int(jpeg_quality) if output == "jpeg" else None
+        fin = (lambda rs: [self._jpeg_bytes(r, jq) for r in rs]) if output == "jpeg" else (lambda rs: rs)
         task = "sr" if task == "super_resolution" else task
         loader = {"denoise": self.load_denoise_model, "sr": self.load_sr_model,
                   "colorize": self.load_colorize_model, "inpaint": self.load_inpaint_model}[task]
@@ -672,9 +702,9 @@ class RestorationPipeline:
                   "inpaint": lambda im, mk: self.inpaint(im, mask=mk, **pk)}[task]
         masks = list(masks) if masks is not None else [None] * len(images)
         if task == "sr" and isinstance(model, RealESRGANModel):
-            return self._sr_realesrgan_batch(model, list(images), max_batch)
+            return fin(self._sr_realesrgan_batch(model, list(images), max_batch))
         if not isinstance(model, NativeSDModel):
-            return [single(im, mk) for im, mk in zip(images, masks)]
+            return fin([single(im, mk) for im, mk in zip(images, masks)])
         out: List[Optional[Image.Image]] = [None] * len(images)
         nsfw: List[Optional[bool]] = [None] * len(images)
         groups: Dict[tuple, List[int]] = {}
@@ -703,9 +733,10 @@ class RestorationPipeline:
                 ims = [prepared[i][0] for i in chunk]
                 try:
                     if task == "inpaint":
-                        res = self._inpaint_native(model, ims, [prepared[i][1] for i in chunk], p, s, steps, g)
+                        res = self._inpaint_native(model, ims, [prepared[i][1] for i in chunk], p, s, steps, g,
+                                                   jpeg_quality=jq)
                     else:
-                        res = self._img2img(model, ims, p, s, steps, g)
+                        res = self._img2img(model, ims, p, s, steps, g, jpeg_quality=jq)
                         for i, f in zip(chunk, self.last_nsfw or []):
                             nsfw[i] = f
                 except IrxError:
@@ -716,4 +747,4 @@ class RestorationPipeline:
                 for i, r in zip(chunk, res):
                     out[i] = r
         self.last_nsfw = nsfw      # per input image: True = returned black, None = not filtered
-        return out  # type: ignore[return-value]
+        return fin(out)  # type: ignore[return-value]

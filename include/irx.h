@@ -254,6 +254,26 @@ long irx_degrade_jpeg_ws_bytes(int batch, int H, int W);
 int irx_degrade_jpeg(void* stream, const uint8_t* img, int batch, int H, int W, const int* qtables, int rgb,
                      void* ws, uint8_t* out);
 
+/* ---- baseline JPEG encoder (PIL.Image.save(path) on a .jpg name, scripts/generate_predictions.py:83-84: the file
+ * Pillow + libjpeg-turbo writes for an RGB image at a quality, byte for byte: baseline sequential, 4:2:0, the
+ * Annex K Huffman tables, no restart markers).  A file is irx_jpeg_header's bytes, the scan, FF D9. ---- */
+/* Device memory irx_jpeg_encode needs as ws (16-byte aligned), and the capacity in bytes it needs per image in
+ * out: 2 * (6 * MCUs * 208) + 2, from 1660 bits per 8x8 block at most (22 of DC, 63 x 26 of AC) and one stuffed
+ * 0x00 per byte at worst.  0 is returned for arguments irx_jpeg_encode would refuse. */
+long irx_jpeg_encode_ws_bytes(int batch, int H, int W);
+long irx_jpeg_encode_bound(int H, int W);
+/* The entropy-coded scan of every image of img [batch][H][W][3] (device uint8; rgb != 0: R,G,B order, else B,G,R)
+ * under image b's tables qtables[b][2][64] (device int; luma, chroma; natural order, 1..255).  8 <= H, W <= 65535.
+ * Image b's scan goes to out + b * out_stride (device; out_stride >= irx_jpeg_encode_bound(H, W)), its length to
+ * lens[b] (device int); exactly lens[b] bytes of image b are written and nothing else in out.  ws may hold
+ * anything on entry. */
+int irx_jpeg_encode(void* stream, const uint8_t* img, int batch, int H, int W, const int* qtables, int rgb, void* ws,
+                    uint8_t* out, long out_stride, int* lens);
+/* Host only: the bytes in front of the scan (SOI, APP0, DQT x 2, SOF0, DHT x 4, SOS; 623 of them) for an H x W
+ * image and the host tables qtables[2][64] (natural order).  Returns the length written to buf (capacity cap), or
+ * a negative status with irx_last_error set. */
+int irx_jpeg_header(int H, int W, const int* qtables, uint8_t* buf, int cap);
+
 /* ---- fast non-local means (cv2.fastNlMeansDenoising / ...Colored as src/inference.py:509-515 calls them in the
  * classical denoise fallback _denoise_opencv :500-522).  OpenCV's integer invoker, exact. ---- */
 /* Host only: the invoker's weight table (almost_dist2weight) for filter strength h over `cn`-channel groups,

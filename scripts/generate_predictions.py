@@ -10,6 +10,10 @@ Modes:
                    classical fallbacks (src/inference.py:859-870);
   --mode batched   runs the diffusion path in engine batches of --batch equal-size images
                    (`RestorationPipeline.restore_batch`).
+
+--encode gpu (batched mode; default pil) writes a chunk whose names all end in .jpg / .jpeg from the bytes of
+`restore_batch(output="jpeg")`: the file PIL's save would write (quality 75), encoded on the device, so only the
+file bytes cross to the host.  A chunk with any other name, and faithful mode, save through PIL as before.
 """
 from __future__ import annotations
 
@@ -39,6 +43,9 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--random-weights", action="store_true", help="seeded random SD-1.5 weights (smoke runs)")
     ap.add_argument("--dtype", default=None, help="engine dtype: fp16 (default, the reference GPU dtype) | bf16 | fp32")
+    ap.add_argument("--encode", default="pil", choices=["pil", "gpu"],
+                    help="gpu (with --mode batched): .jpg / .jpeg outputs are encoded on the device, the same bytes "
+                         "PIL's save writes; every other name, and faithful mode, go through PIL")
     a = ap.parse_args()
     # the driver needs no data collectives (shards are independent; one closing barrier): gloo, so several
     # ranks may also share one GPU
@@ -90,6 +97,13 @@ def main():
                 chunk = mine[k:k + a.batch]
                 imgs = [Image.open(p).convert("RGB") for p in chunk]
                 masks = [mask_for(p) for p in chunk] if task == "inpaint" else None
+                if a.encode == "gpu" and all(p.suffix.lower() in (".jpg", ".jpeg") for p in chunk):
+                    # PIL's save picks JPEG by the extension, at its default quality of 75
+                    outs = pipe.restore_batch(ENGINE_TASK[task], imgs, masks=masks, max_batch=a.batch,
+                                              output="jpeg", jpeg_quality=75)
+                    for p, o in zip(chunk, outs):
+                        (out_dir / p.name).write_bytes(o)
+                    continue
                 outs = pipe.restore_batch(ENGINE_TASK[task], imgs, masks=masks, max_batch=a.batch)
                 for p, o in zip(chunk, outs):
                     o.save(out_dir / p.name)
