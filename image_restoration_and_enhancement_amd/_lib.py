@@ -47,6 +47,17 @@ class ModelConfig(C.Structure):
     ]
 
 
+class JpegInfo(C.Structure):
+    """irx_jpeg_info (include/irx.h): what irx_jpeg_parse reads out of a file."""
+    _fields_ = [("H", C.c_int), ("W", C.c_int), ("ncomp", C.c_int),
+                ("qsel", C.c_int * 3), ("dcsel", C.c_int * 3), ("acsel", C.c_int * 3),
+                ("qt", (C.c_uint16 * 64) * 2),
+                ("dc_bits", (C.c_uint8 * 16) * 2), ("dc_vals", (C.c_uint8 * 16) * 2),
+                ("ac_bits", (C.c_uint8 * 16) * 2), ("ac_vals", (C.c_uint8 * 256) * 2),
+                ("dc_count", C.c_int * 2), ("ac_count", C.c_int * 2),
+                ("scan_off", C.c_long), ("scan_len", C.c_long)]
+
+
 class ParamInfo(C.Structure):
     _fields_ = [("name", C.c_char_p), ("layout", C.c_int), ("dtype", C.c_int), ("ndim", C.c_int),
                 ("shape", C.c_int64 * 4), ("offset", C.c_size_t), ("bytes", C.c_size_t),
@@ -128,6 +139,9 @@ _SIGS = {
     "irx_jpeg_encode_bound": (i64, [i32, i32]),
     "irx_jpeg_encode": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp, i64, vp]),
     "irx_jpeg_header": (i32, [i32, i32, vp, vp, i32]),
+    "irx_jpeg_parse": (i32, [vp, i64, vp]),
+    "irx_jpeg_decode_ws_bytes": (i64, [vp, i32, i32]),
+    "irx_jpeg_decode": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "irx_nlm_weights": (i32, [f32, i32, i32, i32, C.POINTER(i32), i32, C.POINTER(i32)]),
     "irx_nlmeans_u8": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32]),
     "irx_bilateral_tables": (i32, [i32, C.c_double, C.c_double, i32, vp, vp, vp, i32, C.POINTER(i32),

@@ -526,6 +526,23 @@ int irx_jpeg_encode(void* s, const uint8_t* img, int batch, int H, int W, const 
   IRX_API_END
 }
 
+// ------------------------------------------------------------------ baseline JPEG decoder (irx_jpeg_parse: jpeg_parse.cpp)
+long irx_jpeg_decode_ws_bytes(const irx_jpeg_info* infos, int batch, int subseq_bits) {
+  return jpeg_decode_ws_bytes(infos, batch, subseq_bits);
+}
+int irx_jpeg_decode(void* s, const uint8_t* scans, const long* scan_off, const irx_jpeg_info* infos, int batch,
+                    int subseq_bits, int rgb, void* ws, uint8_t* out, const long* out_off, int* status, int* rounds,
+                    int16_t* coef, const long* coef_off) {
+  IRX_API_BEGIN
+  IRX_CHECK(batch >= 0, "JPEG decode: bad arguments");
+  IRX_CHECK(batch == 0 || (scans && scan_off && infos && ws && out && out_off && status && rounds),
+            "JPEG decode: bad arguments");
+  IRX_CHECK(!coef || coef_off, "JPEG decode: coef without coef_off");
+  if (batch)
+    jpeg_decode(scans, scan_off, infos, batch, subseq_bits, rgb, ws, out, out_off, status, rounds, coef, coef_off, S(s));
+  IRX_API_END
+}
+
 // ------------------------------------------------------------------ fast non-local means
 static int nlm_shift(int tmpl) {
   int s = 0;

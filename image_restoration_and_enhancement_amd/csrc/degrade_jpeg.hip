@@ -15,36 +15,14 @@
 // whole MCUs, but chroma ROWS are replicated after down-sampling (the last down-sampled row repeats), and the
 // up-sampler clamps its neighbours at exactly ceil(H/2) x ceil(W/2), not at the padded extents.
 // The forward half (colour conversion, down-sampling, forward DCT, the quantiser's division) lives in jpeg_fdct.h,
-// shared with the baseline encoder (jpeg_encode.hip).
-#include "jpeg_fdct.h"
+// shared with the baseline encoder (jpeg_encode.hip); the inverse half (IDCT passes, output stage, up-sampling,
+// colour conversion back) in jpeg_idct.h, shared with the baseline decoder (jpeg_decode.hip).
+#include "jpeg_idct.h"
 
 namespace irx {
 namespace {
 
 using namespace jpegdev;
-
-// jidctint.c, one 1-D pass in place, descaled by n bits (columns: 11, rows: 18)
-template <int n>
-__device__ __forceinline__ void idct8(int c[8]) {
-  int z2 = c[2], z3 = c[6];
-  int z1 = (z2 + z3) * kC0541;
-  int t2 = z1 - z3 * kC1847, t3 = z1 + z2 * kC0765;
-  int t0 = (c[0] + c[4]) << kConstBits, t1 = (c[0] - c[4]) << kConstBits;
-  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-  t0 = c[7]; t1 = c[5]; t2 = c[3]; t3 = c[1];
-  z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2;
-  int z4 = t1 + t3;
-  const int z5 = (z3 + z4) * kC1175;
-  t0 *= kC0298; t1 *= kC2053; t2 *= kC3072; t3 *= kC1501;
-  z1 *= -kC0899; z2 *= -kC2562;
-  z3 = z3 * -kC1961 + z5;
-  z4 = z4 * -kC0390 + z5;
-  t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
-  c[0] = descale(t10 + t3, n); c[7] = descale(t10 - t3, n);
-  c[1] = descale(t11 + t2, n); c[6] = descale(t11 - t2, n);
-  c[2] = descale(t12 + t1, n); c[5] = descale(t12 - t1, n);
-  c[3] = descale(t13 + t0, n); c[4] = descale(t13 - t0, n);
-}
 
 __device__ __forceinline__ int quant_dequant(int c, int q) { return quantise(c, q) * q; }
 
@@ -67,7 +45,7 @@ __global__ __launch_bounds__(kJT) void jpeg_block_kernel(const uint8_t* __restri
     fdct8<false>(d);
 #pragma unroll
     for (int e = 0; e < 8; ++e) d[e] = quant_dequant(d[e], min(max(q[e * 8], 1), 255));
-    idct8<kConstBits - kPass1Bits>(d);
+    idct8<kIdctColBits>(d);
 #pragma unroll
     for (int e = 0; e < 8; ++e) p[e * kJRow] = d[e];
   }
@@ -76,13 +54,8 @@ __global__ __launch_bounds__(kJT) void jpeg_block_kernel(const uint8_t* __restri
     const int* p = blk + bi * kJBlkStride + l * kJRow;
 #pragma unroll
     for (int e = 0; e < 8; ++e) d[e] = p[e];
-    idct8<kConstBits + kPass1Bits + 3>(d);
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      lo |= (uint32_t)min(max(d[e] + 128, 0), 255) << (8 * e);
-      hi |= (uint32_t)min(max(d[e + 4] + 128, 0), 255) << (8 * e);
-    }
+    idct8<kIdctRowBits>(d);
+    const uint2 row = pack_row(d);
     if (x0 + 16 * mcu < W16) {
       uint8_t* dst;
       if (bk < 4) {
@@ -90,7 +63,7 @@ __global__ __launch_bounds__(kJT) void jpeg_block_kernel(const uint8_t* __restri
       } else {
         dst = (bk == 4 ? cbp : crp) + ((long)b * (H16 / 2) + y0 / 2 + l) * (W16 / 2) + x0 / 2 + 8 * mcu;
       }
-      *reinterpret_cast<uint2*>(dst) = uint2{lo, hi};        // planes are 8-aligned: widths are multiples of 8
+      *reinterpret_cast<uint2*>(dst) = row;                 // planes are 8-aligned: widths are multiples of 8
     }
   }
 }
@@ -104,29 +77,8 @@ __global__ __launch_bounds__(256) void jpeg_upsample_kernel(const uint8_t* __res
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)B * H * CW) return;
   const int cx = (int)(i % CW), y = (int)((i / CW) % H), b = (int)(i / ((long)CW * H));
-  const int cy = y >> 1, ny = min(max((y & 1) ? cy + 1 : cy - 1, 0), CH - 1);
-  const int xl = max(cx - 1, 0), xr = min(cx + 1, CW - 1);
-  int c[2][2];                                               // [Cb, Cr][even, odd pixel], level-shifted
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const uint8_t* pl = (k ? crp : cbp) + (long)b * (H16 / 2) * (W16 / 2);
-    const uint8_t* r0 = pl + (long)cy * (W16 / 2);
-    const uint8_t* r1 = pl + (long)ny * (W16 / 2);
-    const int sl = 3 * r0[xl] + r1[xl], sc = 3 * r0[cx] + r1[cx], sr = 3 * r0[xr] + r1[xr];
-    c[k][0] = ((3 * sc + sl + 8) >> 4) - 128;
-    c[k][1] = ((3 * sc + sr + 7) >> 4) - 128;
-  }
-  const uint8_t* yr = yp + ((long)b * H16 + y) * W16 + 2 * cx;
-  uint8_t* o = out + (((long)b * H + y) * W + 2 * cx) * 3;
-  const int ir = rgb ? 0 : 2, ib = 2 - ir;
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    if (2 * cx + e >= W) break;
-    const int Y = yr[e], cb = c[0][e], cr = c[1][e];
-    o[3 * e + ir] = (uint8_t)min(max(Y + ((FIX16(1.402) * cr + 32768) >> 16), 0), 255);
-    o[3 * e + 1] = (uint8_t)min(max(Y + ((-FIX16(.34414) * cb + 32768 - FIX16(.71414) * cr) >> 16), 0), 255);
-    o[3 * e + ib] = (uint8_t)min(max(Y + ((FIX16(1.772) * cb + 32768) >> 16), 0), 255);
-  }
+  upsample_pair(yp + (long)b * H16 * W16, cbp + (long)b * (H16 / 2) * (W16 / 2), crp + (long)b * (H16 / 2) * (W16 / 2), H,
+                W, W16, rgb, cx, y, out + (long)b * H * W * 3);
 }
 
 inline long pad16(int v) { return ((long)v + 15) & ~15L; }

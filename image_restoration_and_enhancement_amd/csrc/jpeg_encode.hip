@@ -29,6 +29,7 @@
 // 11 bits, + 11 value bits) + 63 x (16 + 10) bits of AC = 1660 bits <= 208 bytes.  Unstuffed scan <= 6 * MCUs * 208
 // bytes; stuffed <= twice that, + 2 (jpeg_encode_bound).  LDS of the coder: 48 * 1660 bits + 31 bits of alignment
 // -> 2492 dwords of bit buffer (9968 B), 536 dwords of code tables (2144 B), 2 x 49 ints of block totals: 12.5 KB.
+#include "block_scan.h"
 #include "jpeg_fdct.h"
 #include "jpeg_tables.h"
 
@@ -94,37 +95,7 @@ __global__ __launch_bounds__(kJT) void jpeg_coef_kernel(const uint8_t* __restric
   }
 }
 
-// ------------------------------------------------------------------ block-wide exclusive scan (kScanT lanes)
-template <typename T>
-__device__ __forceinline__ T wave_incl_scan(T x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
-// exclusive prefix of v over the 256 lanes of the block; *total: the block's sum.  `part`: 4 shared slots.
-template <typename T>
-__device__ __forceinline__ T block_excl_scan(T v, T* part, T* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const T incl = wave_incl_scan(v, lane);
-  __syncthreads();                                           // part[] of a previous call has been read
-  if (lane == 63) part[wave] = incl;
-  __syncthreads();
-  T before = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const T p = part[w];
-    before += w < wave ? p : 0;
-    sum += p;
-  }
-  *total = sum;
-  return before + incl - v;
-}
-
-// ------------------------------------------------------------------ 2, 4: the Huffman coder
+// ------------------------------------------------------------------ 2, 4: the Huffman coder (scans: block_scan.h)
 template <bool EMIT>
 __global__ __launch_bounds__(kHT) void jpeg_huff_kernel(const int16_t* __restrict__ coef, int nmcu, int ngroups,
                                                         long* __restrict__ wgbits, uint32_t* __restrict__ stream,

@@ -3,6 +3,8 @@
 #pragma once
 #include "irx_common.h"
 
+struct irx_jpeg_info;   // include/irx.h
+
 namespace irx {
 
 // ------------------------------------------------------------ implicit-GEMM convolution / GEMM
@@ -359,6 +361,12 @@ long jpeg_encode_bound(int H, int W);
 long jpeg_encode_ws_bytes(int B, int H, int W);
 void jpeg_encode(const uint8_t* img, int B, int H, int W, const int* qt_dev, int rgb, void* ws, uint8_t* out,
                  long out_stride, int* lens, hipStream_t s);
+// baseline JPEG decoder (jpeg_decode.hip; arguments as irx_jpeg_decode, include/irx.h): infos, scan_off, out_off and
+// coef_off are host arrays; ws of jpeg_decode_ws_bytes, 16-byte aligned, contents arbitrary; subseq_bits 0: default
+long jpeg_decode_ws_bytes(const irx_jpeg_info* infos, int B, int subseq_bits);
+void jpeg_decode(const uint8_t* scans, const long* scan_off, const irx_jpeg_info* infos, int B, int subseq_bits,
+                 int rgb, void* ws, uint8_t* out, const long* out_off, int* status, int* rounds, int16_t* coef,
+                 const long* coef_off, hipStream_t s);
 
 
 // ------------------------------------------------------------ fast non-local means (nlmeans.hip)

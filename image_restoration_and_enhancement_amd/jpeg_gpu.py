@@ -6,11 +6,21 @@ then a Huffman coder with one wavefront per 8x8 block, bit placement by prefix s
 back one array of lengths and then the used bytes only; the 623 header bytes (`irx_jpeg_header`) and the EOI marker
 are added on the host.  A CPU tensor goes through `jpeg_host.encode`, the numpy statement of the same coder.
 
-Out of scope: grayscale (`L`) files, PNG, optimised or progressive JPEG, other subsamplings, decoding.
+`decode` is the other direction, `PIL.Image.open(path).convert("RGB")` (the reference's src/metrics.py:40-46 and
+scripts/generate_predictions.py:68) with the pixels born on the device: the host walks the markers
+(`irx_jpeg_parse`), the entropy-coded bytes of the whole batch go up in one copy, `irx_jpeg_decode`
+(csrc/jpeg_decode.hip: a self-synchronising Huffman decoder, then the pixel half of the JPEG round trip) writes the
+images, and one array of statuses comes back.  A file outside the contract (anything but baseline 8-bit 4:2:0 or
+grayscale, one scan, no restart markers) or with a non-zero status is decoded by PIL instead and uploaded, so
+the call returns what PIL returns or raises what PIL raises; `last_fallbacks` names those files.
+
+Out of scope of the encoder: grayscale (`L`) files, PNG, optimised or progressive JPEG, other subsamplings.
 """
 from __future__ import annotations
 
 import ctypes as C
+import io
+import os
 from pathlib import Path
 from typing import List, Sequence, Union
 
@@ -101,3 +111,129 @@ def save(batch_u8: torch.Tensor, paths: Sequence[Union[str, Path]], quality: Uni
         raise ValueError("one path per image")
     for f, p in zip(files, paths):
         Path(p).write_bytes(f)
+
+
+# ------------------------------------------------------------------------------------------------ decoding
+# indices (into the `files` of the last `decode` call) that PIL decoded: refused by the parser, or a non-zero status
+last_fallbacks: List[int] = []
+# the statuses behind them: the parser's negative status, or the decoder's positive one
+last_fallback_status: List[int] = []
+
+
+def parse(data: bytes):
+    """`irx_jpeg_parse` on a file -> (status, JpegInfo): status 0, or a negative refusal (include/irx.h)."""
+    info = L.JpegInfo()
+    buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data if data else b"\0")
+    st = L.load().irx_jpeg_parse(C.cast(buf, C.c_void_p), len(data), C.byref(info))
+    return int(st), info
+
+
+def _read(f) -> bytes:
+    if isinstance(f, (bytes, bytearray, memoryview)):
+        return bytes(f)
+    return Path(os.fspath(f)).read_bytes()
+
+
+def _pil_pixels(data: bytes, mode: str) -> np.ndarray:
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        return np.array(im.convert(mode))
+
+
+def _shape(info, mode: str):
+    return (info.H, info.W, 3) if mode == "RGB" else (info.H, info.W)
+
+
+def decode_device(datas: Sequence[bytes], infos, mode: str, device, subseq_bits: int = 0, want_coef: bool = False):
+    """`irx_jpeg_decode` on parsed files: -> (images, status list, rounds list[, coefficient tensors]).  One H2D copy
+    of the scans, one D2H copy of status and rounds."""
+    B = len(datas)
+    arr = (L.JpegInfo * B)(*infos)
+    lens = [int(i.scan_len) for i in infos]
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    host = np.empty(int(offs[-1]), np.uint8)
+    for b, (d, i) in enumerate(zip(datas, infos)):
+        host[offs[b]:offs[b + 1]] = np.frombuffer(d, np.uint8, lens[b], int(i.scan_off))
+    scans = torch.from_numpy(host).to(device)                                  # H2D: the entropy-coded bytes
+    nws = int(L.call("irx_jpeg_decode_ws_bytes", C.cast(arr, C.c_void_p), B, subseq_bits))
+    if nws <= 0:
+        raise L.IrxError("irx_jpeg_decode: refused arguments")
+    ws = torch.empty(nws, dtype=torch.uint8, device=device)
+    ch = 3 if mode == "RGB" else 1
+    sizes = [i.H * i.W * ch for i in infos]
+    ooff = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    out = torch.empty(int(ooff[-1]), dtype=torch.uint8, device=device)
+    sr = torch.empty((2, B), dtype=torch.int32, device=device)
+    coef, coff = None, None
+    if want_coef:
+        nb = [_nblocks(i) * 64 for i in infos]
+        coff = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
+        coef = torch.empty(int(coff[-1]), dtype=torch.int16, device=device)
+    with torch.cuda.device(scans.device):
+        L.call("irx_jpeg_decode", _s(), _p(scans), offs.ctypes.data_as(C.c_void_p), C.cast(arr, C.c_void_p), B,
+               subseq_bits, int(mode == "RGB"), _p(ws), _p(out), ooff.ctypes.data_as(C.c_void_p), _p(sr[0]), _p(sr[1]),
+               _p(coef) if want_coef else None, coff.ctypes.data_as(C.c_void_p) if want_coef else None)
+    srh = sr.cpu().tolist()                                                    # D2H: status and rounds
+    imgs = [out[ooff[b]:ooff[b + 1]].view(_shape(infos[b], mode)) for b in range(B)]
+    if want_coef:
+        return imgs, srh[0], srh[1], [coef[coff[b]:coff[b + 1]].view(-1, 64) for b in range(B)]
+    return imgs, srh[0], srh[1]
+
+
+def _nblocks(info) -> int:
+    if info.ncomp == 3:
+        return 6 * (-(-info.H // 16)) * (-(-info.W // 16))
+    return (-(-info.H // 8)) * (-(-info.W // 8))
+
+
+def decode(files: Sequence[Union[bytes, str, Path]], mode: str = "RGB", device="cuda",
+           subseq_bits: int = 0) -> List[torch.Tensor]:
+    """JPEG files (bytes or paths) -> uint8 tensors on `device`, in input order: [H][W][3] for mode "RGB", [H][W] for
+    mode "L"; each equal to `np.asarray(PIL.Image.open(f).convert(mode))`.  Files the device decoder does not take
+    (see the head of this module; for mode "L" also every colour file) go through PIL; what PIL raises is raised.
+    On a CPU device the pixels come from `jpeg_host.decode` / PIL."""
+    global last_fallbacks, last_fallback_status
+    if mode not in ("RGB", "L"):
+        raise ValueError("mode 'RGB' or 'L'")
+    device = torch.device(device)
+    datas = [_read(f) for f in files]
+    res: List[torch.Tensor] = [None] * len(datas)
+    fallbacks, statuses = {}, {}
+    if device.type != "cuda":
+        for b, d in enumerate(datas):
+            try:
+                info = JH.parse(d)
+                if mode == "L" and info["ncomp"] != 1:
+                    raise JH.Refused(JH.E_COMPONENTS, "mode L of a colour file")
+                res[b] = torch.from_numpy(JH.pixels(JH.decode_coefficients(d, info), info, mode))
+            except JH.Refused as e:
+                fallbacks[b] = e.status
+                res[b] = torch.from_numpy(_pil_pixels(d, mode))
+        last_fallbacks, last_fallback_status = sorted(fallbacks), [fallbacks[b] for b in sorted(fallbacks)]
+        return res
+    good, infos = [], []
+    for b, d in enumerate(datas):
+        st, info = parse(d)
+        if st == 0 and mode == "L" and info.ncomp != 1:
+            st = JH.E_COMPONENTS
+        if st == 0:
+            good.append(b)
+            infos.append(info)
+        else:
+            fallbacks[b] = st
+    if good:
+        imgs, status, _ = decode_device([datas[b] for b in good], infos, mode, device, subseq_bits)
+        for j, b in enumerate(good):
+            if status[j]:
+                fallbacks[b] = status[j]
+            else:
+                res[b] = imgs[j]
+    for b in sorted(fallbacks):
+        res[b] = torch.from_numpy(_pil_pixels(datas[b], mode)).to(device)
+    last_fallbacks, last_fallback_status = sorted(fallbacks), [fallbacks[b] for b in sorted(fallbacks)]
+    return res
+
+
+def open(path: Union[str, Path, bytes], mode: str = "RGB", device="cuda") -> torch.Tensor:
+    """`decode` of a single file."""
+    return decode([path], mode, device)[0]

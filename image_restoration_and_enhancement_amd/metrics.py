@@ -57,8 +57,21 @@ _XYZ_FROM_RGB = np.array([[0.412453, 0.357580, 0.180423],
 _WHITE_D65 = np.array([0.95047, 1.0, 1.08883])
 
 
-def load_image(path: Path) -> np.ndarray:
-    """Load image as RGB uint8 HWC (reference `src/metrics.py:40-46`)."""
+def load_image(path: Path, device=None):
+    """Load image as RGB uint8 HWC (reference `src/metrics.py:40-46`).  With a `cuda*` device and a .jpg / .jpeg name
+    the file is decoded on the GPU (`jpeg_gpu.open`, csrc/jpeg_decode.hip; the same pixels) and the result is a uint8
+    device tensor; otherwise, and where the native path is not available, a numpy array, as ever."""
+    if device is not None and str(device).startswith("cuda") and Path(path).suffix.lower() in (".jpg", ".jpeg"):
+        try:
+            from . import _lib, jpeg_gpu
+            try:
+                return jpeg_gpu.open(Path(path), "RGB", device)
+            except _lib.IrxError:       # no library, or an argument the op refuses (a scan above 128 MiB): PIL below
+                pass
+        except ImportError:             # no torch
+            pass
+        except (OSError, ValueError):
+            raise ValueError(f"Could not load image: {path}")
     try:
         with Image.open(str(path)) as im:
             return np.array(im.convert("RGB"))
@@ -244,10 +257,16 @@ class MetricsCalculator:
     `device="cpu"` (the default) is the numpy code above.  A `cuda*` string or torch.device scores on the GPU
     (`metrics_gpu`, csrc/metrics.hip) when one is visible, `libirx.so` loads and the pair's shape is inside the
     kernel's range (H, W >= 7, 1 or 3 channels); any other pair takes the numpy code.  Every method accepts numpy
-    images or uint8 device tensors ([H, W] or [H, W, C]), so `restore_batch` outputs are scored without a download."""
+    images or uint8 device tensors ([H, W] or [H, W, C]), so `restore_batch` outputs are scored without a download.
+
+    `decode="gpu"` makes `load` decode .jpg / .jpeg files on that GPU (`load_image(path, device)`), so the pixels of a
+    pair never visit the host; `decode="pil"` (the default), a CPU device and every other file type load with PIL."""
 
     def __init__(self, use_lpips: bool = True, use_fid: bool = True, device: str = "cpu", lpips_weights=None,
-                 fid_weights=None):
+                 fid_weights=None, decode: str = "pil"):
+        if decode not in ("pil", "gpu"):
+            raise ValueError("decode must be 'pil' or 'gpu'")
+        self.decode = decode
         self._lpips_w = resolve_lpips_weights(lpips_weights) if use_lpips else None
         self.use_lpips = self._lpips_w is not None
         self._fid_w = resolve_fid_weights(fid_weights) if use_fid else None
@@ -271,6 +290,12 @@ class MetricsCalculator:
                 except Exception:   # no torch, no library: the host code serves
                     self._gpu = None
         return self._gpu
+
+    def load(self, path):
+        """`load_image(path)`, on the device where `decode="gpu"` and the GPU path is up."""
+        if self.decode == "gpu" and self._gpu_module() is not None:
+            return load_image(path, self.device)
+        return load_image(path)
 
     def _device_pair(self, pred, gt, channels=(1, 3)):
         """(pred, gt) as uint8 device tensors of gt's shape (pred resized on the GPU if its size differs), or None
@@ -397,17 +422,20 @@ _EXTS = {".jpg", ".jpeg", ".png"}
 
 
 def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_lpips: bool = True,
-                  use_fid: bool = True, device: str = "cpu", lpips_weights=None, fid_weights=None) -> dict:
+                  use_fid: bool = True, device: str = "cpu", lpips_weights=None, fid_weights=None,
+                  decode: str = "pil") -> dict:
     """Match predictions to ground truth by file name (any of .jpg/.jpeg/.png) and aggregate
     mean/std/min/max/median per metric (reference `src/metrics.py:238-348`).  With a `cuda*` device the pairs are
     scored on the GPU as they are loaded and read back together, one synchronisation per task.  LPIPS is reported
     when weights are configured (`lpips_weights` or `IRX_LPIPS_WEIGHTS`); a pair it refuses (a side below 31 px) is
     skipped whole, as the reference skips a pair whose `calculate_all` raises.  FID is reported (`fid`, one value)
     when weights are configured (`fid_weights` or `IRX_FID_WEIGHTS`): each scored pair's Inception features are
-    taken as the loop runs — the reference keeps every image in a list instead — and read back with the rest."""
+    taken as the loop runs — the reference keeps every image in a list instead — and read back with the rest.
+    `decode="gpu"` (with a `cuda*` device) decodes the .jpg / .jpeg files of the pairs on the GPU as well
+    (`jpeg_gpu`), so their pixels never visit the host; the result is the same to the last bit."""
     pred_dir, gt_dir = Path(pred_dir), Path(gt_dir)
     calc = MetricsCalculator(use_lpips=use_lpips, use_fid=use_fid, device=device, lpips_weights=lpips_weights,
-                             fid_weights=fid_weights)
+                             fid_weights=fid_weights, decode=decode)
     pred_files = sorted(f for f in pred_dir.iterdir() if f.suffix.lower() in _EXTS)
     gt_names = {f.name for f in gt_dir.iterdir() if f.suffix.lower() in _EXTS}
     if len(pred_files) != len(gt_names):
@@ -439,7 +467,7 @@ def evaluate_task(pred_dir: Path, gt_dir: Path, task_name: str = "denoise", use_
             fid_error = e
     for i, (pp, gp) in enumerate(pairs):
         try:
-            pred, gt = load_image(pp), load_image(gp)
+            pred, gt = calc.load(pp), calc.load(gp)
             pair = calc._device_pair(pred, gt)
             if pair is not None:                # enqueued; read back after the loop, all pairs in one download
                 # LPIPS first: a pair it refuses raises here, before any slot of the pair exists

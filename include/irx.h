@@ -274,6 +274,67 @@ int irx_jpeg_encode(void* stream, const uint8_t* img, int batch, int H, int W, c
  * a negative status with irx_last_error set. */
 int irx_jpeg_header(int H, int W, const int* qtables, uint8_t* buf, int cap);
 
+/* ---- baseline JPEG decoder (PIL.Image.open(path).convert("RGB"), src/metrics.py:40-46 load_image and
+ * scripts/generate_predictions.py:68: the pixels Pillow + libjpeg-turbo decode, bit for bit).  The contract is the
+ * kind of file PIL.save and cv2.imwrite write by default: baseline SOF0, 8 bit, one scan, no restart interval, JFIF,
+ * either 4:2:0 with sampling (2,2)(1,1)(1,1) or one component.  Everything else is refused by the parser and stays
+ * with PIL. ---- */
+/* What irx_jpeg_parse reads out of a file (plain data, no pointers). */
+typedef struct irx_jpeg_info {
+  int H, W;                    /* 8 .. 65535 */
+  int ncomp;                   /* 1 (grayscale) or 3 (Y, Cb, Cr at 4:2:0) */
+  int qsel[3], dcsel[3], acsel[3]; /* per component: quantisation, DC and AC Huffman table, each 0 or 1 */
+  uint16_t qt[2][64];          /* quantisation tables, natural (row-major) order; 0: the file defines none */
+  uint8_t dc_bits[2][16];      /* DC tables: codes per length 1..16, then the symbols in code order */
+  uint8_t dc_vals[2][16];
+  uint8_t ac_bits[2][16];      /* AC tables likewise */
+  uint8_t ac_vals[2][256];
+  int dc_count[2], ac_count[2]; /* symbols per table; 0: the file defines none */
+  long scan_off, scan_len;     /* the entropy-coded bytes: file[scan_off .. scan_off + scan_len), up to the first
+                                  FF xx with xx != 00 (which is the EOI marker) */
+} irx_jpeg_info;
+/* irx_jpeg_parse's refusals; each sets irx_last_error */
+#define IRX_JPEG_TRUNCATED (-1)   /* the file ends inside the header or a segment */
+#define IRX_JPEG_NOT_JPEG (-2)    /* empty, or no SOI */
+#define IRX_JPEG_SOF (-3)         /* SOF1, SOF2, ...: extended, progressive, lossless or arithmetic coding */
+#define IRX_JPEG_PRECISION (-4)   /* sample precision other than 8 bits */
+#define IRX_JPEG_DQT16 (-5)       /* 16-bit quantisation table */
+#define IRX_JPEG_SAMPLING (-6)    /* three components sampled other than (2,2)(1,1)(1,1) */
+#define IRX_JPEG_MULTISCAN (-7)   /* a scan without every component, or data after the scan other than EOI */
+#define IRX_JPEG_DRI (-8)         /* a non-zero restart interval, or a restart marker in the scan */
+#define IRX_JPEG_ADOBE (-9)       /* Adobe APP14 marker (a colour transform PIL honours) */
+#define IRX_JPEG_RGB_IDS (-10)    /* component ids 'R','G','B' (libjpeg takes the file for RGB) */
+#define IRX_JPEG_COMPONENTS (-11) /* CMYK / YCCK, or a component count other than 1 or 3 */
+#define IRX_JPEG_SIZE (-12)       /* H or W below 8 (the inverse half's minimum, as irx_degrade_jpeg) */
+#define IRX_JPEG_TABLES (-13)     /* a table id above 1, a table that is named but not defined, DC category > 11,
+                                     AC size > 10 */
+#define IRX_JPEG_SCAN_CUT (-14)   /* the file ends inside the scan */
+#define IRX_JPEG_MALFORMED (-15)  /* anything else that is not a well-formed file */
+/* Host only.  Walks the markers of file[0 .. len) and fills *info; APPn and COM are skipped, the Huffman tables are
+ * the file's own.  Returns 0, or one of the statuses above.  Never reads past len. */
+int irx_jpeg_parse(const uint8_t* file, long len, irx_jpeg_info* info);
+/* Device memory irx_jpeg_decode needs as ws (16-byte aligned) for these files (host infos) at this subseq_bits;
+ * 0 for arguments irx_jpeg_decode would refuse. */
+long irx_jpeg_decode_ws_bytes(const irx_jpeg_info* infos, int batch, int subseq_bits);
+/* Decodes a batch of parsed files.  scans (device): the entropy-coded bytes of every file, image b's at
+ * scans + scan_off[b], infos[b].scan_len of them (infos[b].scan_off is not used); scan_off, infos, out_off and
+ * coef_off are host arrays of `batch` entries.  subseq_bits: the bits of the stream one lane of the
+ * self-synchronising Huffman decoder owns, a multiple of 32, 32 .. 65536; 0: the default (1024).  rgb != 0: every
+ * image is written as uint8 [H][W][3] R,G,B (a one-component file replicated to three channels); rgb == 0: every
+ * file must have one component and is written as [H][W].  Image b goes to out + out_off[b] (device); exactly its
+ * H * W * C bytes are written and nothing else in out.  status[b] (device int) != 0: the stream of image b is not a
+ * valid scan of its frame (bit 0: an unassigned code or a run past coefficient 63 on the decoded path; bit 1: too few
+ * or too many blocks, or a symbol that runs past the end), or (bit 2) a block's coefficients are so large that
+ * libjpeg's C and SIMD IDCTs disagree; its pixels are unspecified but inside its H * W * C bytes, the other images
+ * are unaffected.  rounds[b] (device int): the most rounds any pass of the
+ * entry-state kernel took.  coef (device, may be NULL): image b's quantised coefficients as int16 [block][64] in
+ * zigzag order at coef + coef_off[b] (in elements; blocks in scan order).  ws may hold anything on entry.  An info
+ * that irx_jpeg_parse did not fill is checked like the parser checks a file (sizes, selectors, and that every Huffman
+ * table has as many symbols as its code counts say and is not over-subscribed) and refused otherwise. */
+int irx_jpeg_decode(void* stream, const uint8_t* scans, const long* scan_off, const irx_jpeg_info* infos, int batch,
+                    int subseq_bits, int rgb, void* ws, uint8_t* out, const long* out_off, int* status, int* rounds,
+                    int16_t* coef, const long* coef_off);
+
 /* ---- fast non-local means (cv2.fastNlMeansDenoising / ...Colored as src/inference.py:509-515 calls them in the
  * classical denoise fallback _denoise_opencv :500-522).  OpenCV's integer invoker, exact. ---- */
 /* Host only: the invoker's weight table (almost_dist2weight) for filter strength h over `cn`-channel groups,
